@@ -10,12 +10,18 @@ with the graph (CSR + fp64 CDF), features and weights resident in HBM.  `value` 
 N > 1: the item catalogue is sharded by id range over N ranks (RCCL all-gather of hidden rows per layer
 and of the [nq, K] candidates), total work fixed -> "scaling": "strong".
 
-Launch: python bench.py --gpus 1 --steps K --warmup W
+Launch: python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
         python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
-Prints ONE JSON line on rank 0.  At N = 1 the line carries `cpu_baseline` (the C oracle + torch CPU on the host cores, the
-whole step) and `parity_check`: that CPU run's outputs compared with one GPU step from the same RNG state -- sampled ids /
-counts of both layers in both RNG modes, the np.random state afterwards, LSH codes and top-k lists bit-exact, embeddings
-within 1e-5; a mismatch exits with status 1 after printing the line.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times exactly K steps and prints the headline (`value`,
+`ms_per_step`, the per-phase split of the same steps).  --full adds what takes runs of its own: a second K-step region with
+an event pair around every kernel launch (`kernels`, `roofline`), at N = 1 the other RNG mode (`other_rng_mode`), and
+`cpu_baseline` (the C oracle + torch CPU on the host cores, the whole step) with `parity_check`: that CPU run's outputs
+compared with one GPU step from the same RNG state -- sampled ids / counts of both layers in both RNG modes, the np.random
+state afterwards, LSH codes and top-k lists bit-exact, embeddings within 1e-5; a mismatch exits with status 1 after printing
+the line.
+--dump-outputs DIR: rank 0 writes what the last timed step returned (embeddings, LSH codes, top-k distances and ids; a fixed,
+seeded sample of rows where the arrays exceed DUMP_BYTES) as DIR/<name>.npy in float32 / float64.  Every step starts from
+the same RNG state (np.random.seed(42), Philox call 0), so the same arguments give the same outputs from run to run.
 """
 import argparse
 import json
@@ -60,6 +66,9 @@ ONDIE_GATHER_PEAK = 18.8e12
 PRESETS = {2: dict(dim=128, T=10, lsh_bits=256), 3: dict(dim=256, T=50, lsh_bits=512),
            5: dict(dim=256, T=10, lsh_bits=512, rng="philox")}
 CONFIG5 = dict(num_users=10_000_000, num_items=100_000_000, num_ratings=1_000_000_000, ranks=8)
+# --dump-outputs: at most this many bytes in all; 48 MiB for the item rows (embeddings + codes), 12 MiB for the query rows
+DUMP_BYTES = 64 << 20
+DUMP_ITEM_ROWS = 32768
 
 
 def parse():
@@ -79,7 +88,11 @@ def parse():
     ap.add_argument("--config", type=int, default=0, choices=[0, 2, 3, 5],
                     help="BASELINE.json config preset: 2 = d128/T10/256-bit, 3 = d256/T50/512-bit (the rocprof roofline run), "
                          "5 = one rank's shard of the 100 M-item / 10^9-rating stress graph (HBM-bound sampler)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also per-kernel timings + roofline, the other RNG mode and the CPU baseline with its parity check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline / parity check")
     ap.add_argument("--cpu-sample", type=int, default=0, help="start items timed on the CPU (0 = the whole catalogue)")
     a = ap.parse_args()
     if a.config:
@@ -203,6 +216,8 @@ def main():
     def step(record=None):
         if a.rng == "numpy":
             np.random.seed(42)
+        else:
+            sampler._calls = 0                 # Philox call 0 on: every step draws the same walks, whatever ran before it
         e0, e1, e2, e3 = ev(), ev(), ev(), ev()
         e0.record()
         emb = pipe.embed(x_loc, T, x_full=x_rep)
@@ -247,24 +262,27 @@ def main():
             emb, d_out, i_out = step(recs_clean)
         sync_all()
         elapsed = time.perf_counter() - t0
-        # ---- instrumented region: the same K steps again with one HIP-event pair around every kernel
-        # launch (on the launch stream) and around the three phases.  Timing events are barrier packets on
-        # ROCm (~46 per step), so this region is slower than the clean one and is NOT used for `value`.
-        timer = nv.KernelTimer()
-        recs = []
-        pipe.overlap_sampling = False       # per-kernel durations are measured with the kernels running alone
-        overlap_proj = pipe.overlap_input_proj
-        pipe.overlap_input_proj = False
-        sync_all()
-        nv.set_timer(timer)
-        t1 = time.perf_counter()
-        for _ in range(a.steps):
-            step(recs)
-        sync_all()
-        elapsed_instr = time.perf_counter() - t1
-        nv.set_timer(None)
-        pipe.overlap_sampling = False
-        pipe.overlap_input_proj = overlap_proj
+        # host copies now: the --full regions below run the step again in the same buffers
+        dump = step_outputs(pipe, emb, d_out, i_out, a.k) if a.dump_outputs and rank == 0 else None
+        if a.full:
+            # ---- instrumented region: the same K steps again with one HIP-event pair around every kernel
+            # launch (on the launch stream) and around the three phases.  Timing events are barrier packets on
+            # ROCm (~46 per step), so this region is slower than the clean one and is NOT used for `value`.
+            timer = nv.KernelTimer()
+            recs = []
+            pipe.overlap_sampling = False       # per-kernel durations are measured with the kernels running alone
+            overlap_proj = pipe.overlap_input_proj
+            pipe.overlap_input_proj = False
+            sync_all()
+            nv.set_timer(timer)
+            t1 = time.perf_counter()
+            for _ in range(a.steps):
+                step(recs)
+            sync_all()
+            elapsed_instr = time.perf_counter() - t1
+            nv.set_timer(None)
+            pipe.overlap_sampling = False
+            pipe.overlap_input_proj = overlap_proj
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -276,19 +294,41 @@ def main():
         phase_ms["query"] += e2.elapsed_time(e3)
     ms_per_step = elapsed / a.steps * 1e3
     value = items_per_step * a.steps / elapsed
-    ksum = timer.summary()
-
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "item embeddings/sec + top-K ANN queries/sec, ML-25M d=256, 1/2/4/8 GPU",
+            "value": value, "unit": "items/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": "f64 cdf / f32 features / fp4 sign planes (exact integer Hamming)", "data": "synthetic",
+            "config": {"workload": (f"SYN-1B (BASELINE config 5: U={U} M={M} R={R} = {2 * R} directed edges, replicated) as rank 0 of "
+                                    f"{sim_ranks} sees it: item shard [{pipe.lo}, {pipe.hi}), gathers of the other ranks' rows stood in "
+                                    f"for by local buffers of the gathered shape (no xGMI time); value = shard items / step; "
+                                    if big else f"SYN-25M (ML-25M-shaped: U={U} M={M} R={R}), ")
+                                   + f"F=128 H=256 d={D}, 2 GCN layers, "
+                                   f"W=100 L=2 T={T}, LSH {nbits}-bit, {nq} queries K={a.k}, rng={a.rng}"
+                                   + (" (the reference's np.random MT19937 stream generated on device: neighbour ids bit-exact with "
+                                      "the reference CPU path)" if a.rng == "numpy" else " (counter-based, shard invariant)")
+                                   + (f", BASELINE config {a.config}" if a.config else ""),
+                       "global_items": M, "items_per_step": items_per_step, "queries": nq,
+                       "parallelism": f"item-shard x{world}" if not big else f"one rank of item-shard x{sim_ranks}"},
+            "embeddings_per_s": items_per_step / (phase_ms["embed"] / a.steps * 1e-3),
+            "index_items_per_s": items_per_step / (phase_ms["index"] / a.steps * 1e-3),
+            "queries_per_s": nq / (phase_ms["query"] / a.steps * 1e-3),
+            "phase_ms": {k: round(v / a.steps, 4) for k, v in phase_ms.items()},
+            "graph_build_s": round(t_graph, 3),
+        }
     gpu_ref = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         gpu_ref = parity_gpu_step(a, graph, pipe, sampler, step, M, T, W, L, LAYERS, big)
-    if big:
+    if a.full and big:
         # the step's buffers (102 GB stand-in, activations) go, the plain graph arrays come back for the accounting / the oracle
         emb = d_out = i_out = None
         pipe.comm._bufs.clear()
         torch.cuda.empty_cache()
         graph.expand()
-    out = None
-    if rank == 0:
+    if a.full and rank == 0:
+        ksum = timer.summary()
         # ---------------- roofline of every kernel (rank 0's shard), algorithmic bytes / flops ---------
         nodes = torch.arange(pipe.lo, pipe.hi, dtype=torch.int64, device=dev)
         n_loc = nodes.numel()
@@ -418,43 +458,56 @@ def main():
         if "ps_hamming_topk_mfma_codes" in kern:
             kern["ps_hamming_topk_mfma_codes"]["unit"] = "TOP/s"
 
-        out = {
-            "metric": "item embeddings/sec + top-K ANN queries/sec, ML-25M d=256, 1/2/4/8 GPU",
-            "value": value, "unit": "items/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f64 cdf / f32 features / fp4 sign planes (exact integer Hamming)", "data": "synthetic",
-            "config": {"workload": (f"SYN-1B (BASELINE config 5: U={U} M={M} R={R} = {2 * R} directed edges, replicated) as rank 0 of "
-                                    f"{sim_ranks} sees it: item shard [{pipe.lo}, {pipe.hi}), gathers of the other ranks' rows stood in "
-                                    f"for by local buffers of the gathered shape (no xGMI time); value = shard items / step; "
-                                    if big else f"SYN-25M (ML-25M-shaped: U={U} M={M} R={R}), ")
-                                   + f"F=128 H=256 d={D}, 2 GCN layers, "
-                                   f"W=100 L=2 T={T}, LSH {nbits}-bit, {nq} queries K={a.k}, rng={a.rng}"
-                                   + (" (the reference's np.random MT19937 stream generated on device: neighbour ids bit-exact with "
-                                      "the reference CPU path)" if a.rng == "numpy" else " (counter-based, shard invariant)")
-                                   + (f", BASELINE config {a.config}" if a.config else ""),
-                       "global_items": M, "items_per_step": items_per_step, "queries": nq,
-                       "parallelism": f"item-shard x{world}" if not big else f"one rank of item-shard x{sim_ranks}"},
-            "embeddings_per_s": items_per_step / (phase_ms["embed"] / a.steps * 1e-3),
-            "index_items_per_s": items_per_step / (phase_ms["index"] / a.steps * 1e-3),
-            "queries_per_s": nq / (phase_ms["query"] / a.steps * 1e-3),
-            "phase_ms": {k: round(v / a.steps, 4) for k, v in phase_ms.items()},
-            "ms_per_step_instrumented": elapsed_instr / a.steps * 1e3,
-            "graph_build_s": round(t_graph, 3),
-            "roofline": roofline, "kernels": kern,
-        }
+        out["ms_per_step_instrumented"] = elapsed_instr / a.steps * 1e3
+        out["roofline"], out["kernels"] = roofline, kern
         if world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"], out["parity_check"] = cpu_baseline(a, graph, pipe, gpu_ref, params, x_loc, A, M, T, W, L,
                                                                     LAYERS, HID, D, nbits, nq, big)
             out["vs_cpu_baseline"] = value / out["cpu_baseline"]["value"]
         if world == 1 and not big:            # config 5: 5 x 10^9 stream uniforms per shard pass -- Philox only
             out["other_rng_mode"] = other_mode_probe(a, graph, params, LAYERS, M, x_loc, A, T, W, L, nq_local)
+    if out is not None:
         print(json.dumps(out), flush=True)
+    if dump is not None:
+        write_outputs(a.dump_outputs, dump)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
     if out is not None and not out.get("parity_check", {}).get("ok", True):
         print(f"bench.py: the GPU step does not match the oracle: {out['parity_check']}", file=sys.stderr)
         sys.exit(1)
+
+
+def step_outputs(pipe, emb, d_out, i_out, k):
+    """Host copies of what the step's caller receives: embeddings and LSH codes of this rank's items (at most DUMP_ITEM_ROWS
+    of them, a fixed seeded sample beyond that; `item_ids` names the rows) and the top-k lists of all queries (a fixed seeded
+    sample of queries beyond 12 MiB; `query_rows` names them).  Integers are exact in the float type they are stored in."""
+    n, nbytes = emb.size(0), pipe.codes.size(1)
+    item_cap = min(DUMP_ITEM_ROWS, (48 << 20) // (emb.size(1) * 4 + nbytes * 4 + 8))
+    q_cap = (12 << 20) // (k * (4 + 8) + 8)
+
+    def rows(total, cap):
+        if total <= cap:
+            return np.arange(total)
+        return np.sort(np.random.RandomState(0).choice(total, size=cap, replace=False))
+
+    r = rows(n, item_cap)
+    q = rows(d_out.size(0), q_cap)
+    rt, qt = torch.from_numpy(r).to(emb.device), torch.from_numpy(q).to(emb.device)
+    out = {"embeddings": emb[rt].float().cpu().numpy(),
+           "codes": pipe.codes[rt].cpu().numpy().astype(np.float32),
+           "item_ids": (r + pipe.lo).astype(np.float64),
+           "topk_dist": d_out[qt].cpu().numpy().astype(np.float32),
+           "topk_ids": i_out[qt].cpu().numpy().astype(np.float64),
+           "query_rows": q.astype(np.float64)}
+    assert sum(v.nbytes for v in out.values()) <= DUMP_BYTES
+    return out
+
+
+def write_outputs(dirname, arrays):
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), v)
 
 
 def other_mode_probe(a, graph, params, LAYERS, M, x_loc, A, T, W, L, nq_local):

@@ -22,7 +22,7 @@ def load(d, counter):
 
 F, Wr = load(fetch_dir, "FETCH_SIZE"), load(write_dir, "WRITE_SIZE")
 names = sorted(set(F) | set(Wr), key=lambda k: -(F[k][0] + Wr[k][0]))
-lines = ["rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only) over `bench.py --steps %d --warmup 1 --no-cpu-baseline`" % steps,
+lines = ["rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only) over `bench.py --full --steps %d --warmup 1 --no-cpu-baseline`" % steps,
          "values: KB per launch (mean over launches), as reported (FETCH_SIZE = TCC_EA0_RDREQ x 64 B; no wide-stream correction applied)", ""]
 for k in names:
     own = any(t in k for t in ("walk_", "gemm_f32", "hamming", "importance_pool", "topk_merge", "slice_merge", "bound_select", "lsh_expand", "cdf_", "guide_", "pack_", "bucket_", "gather_kernel", "mt_", "spmm"))
@@ -63,7 +63,7 @@ def per_call(pred):
     return b / max(n, 1)
 
 
-out = {"source": f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, bench.py --steps {steps} --warmup 1 --no-cpu-baseline ({label})",
+out = {"source": f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, bench.py --full --steps {steps} --warmup 1 --no-cpu-baseline ({label})",
        "units": "bytes per launch = (FETCH_SIZE + WRITE_SIZE) KB * 1024, as reported.  Calibration (profiles/r03_config5/pmc_calibration.txt): narrow gathers (8-byte / 64-byte random reads: the sampler) count exactly one 64-byte sector per request = real fabric traffic; wide coalesced streams count at 0.50 and random 1 KiB rows at 0.28 of their bytes (GEMM operands, pooling rows: multiply before comparing with a byte count)",
        # walk_sample_kernel<NP, STREAM>: the headline (numpy-stream) step launches the STREAM = true kernel; the `other_rng_mode` leg of
        # the same bench run launches the Philox one (listed in the .txt, not part of this figure)
