@@ -222,6 +222,19 @@ int ps_permute_k(const float *W, int64_t rows, int K, int ld, float *out, ps_str
 int ps_linear(const float *x, int64_t M, int K, const float *W, int ldw, const float *b, int N,
               const float *x2, int K2, const float *W2, int ldw2, int flags, float *y, ps_stream_t stream);
 
+/* One layer of the pooled branch in one call: y = epilogue( x W^T + pool(h_full) W2^T + b ), where pool(h_full) is
+ * ps_importance_pool(h_full, n_full, H, ids, counts, wts, nvalid, M, T, max_idx, renorm) and the rest is ps_linear with
+ * x2 = that pooled matrix (K2 = H): the same bits as that pair.  Rows that keep no neighbour skip the K2 half (their pooled row is
+ * +0.0); the pooled rows are never written as a matrix.  Served: N == 256, flags PS_RELU | PS_L2NORM (PS_WPERM allowed),
+ * M >= 24 576, T <= 16, 16-byte aligned operands with K % 32 == 0 and H % 32 == 0; any other call returns PS_EUNSUPPORTED
+ * without doing anything, and so does every call under the environment switch PS_GCN_FUSED=0 -- the caller then runs the pair.
+ * workspace: ps_gcn_layer_workspace_bytes(M, H) bytes, 16-byte aligned, not preserved between calls. */
+size_t ps_gcn_layer_workspace_bytes(int64_t M, int H);
+int ps_gcn_layer(const float *x, int64_t M, int K, const float *W, int ldw, const float *b, int N, const float *h_full,
+                 int64_t n_full, int H, const int32_t *ids, const int32_t *counts, const float *wts, const int32_t *nvalid,
+                 int T, int64_t max_idx, int renorm, const float *W2, int ldw2, int flags, float *y, void *workspace,
+                 size_t workspace_bytes, ps_stream_t stream);
+
 /* ---- a10: LSHIndex.build/search (utils/nearest_neighbors.py:28-68 -> faiss.IndexLSH) ---------
  * codes[n, nbits/8] : bit j = ( x . A[j,:] >= 0 ), LSB-first (faiss fvec2bitvec); A float[nbits,D].
  * flags: 0 or PS_WPERM (A stored by ps_permute_k). */

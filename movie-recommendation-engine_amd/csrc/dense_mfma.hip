@@ -3,6 +3,7 @@
 //   ps_linear     : y = epi( x W^T (+ x2 W2^T) + b ), epi = bias / ReLU / row L2-normalise.
 //                   Replaces the nn.Linear + F.relu + torch.cat + F.normalize chain of
 //                   PinSage.forward (reference model/pinsage.py:202, 235-240, 248-249).
+//   ps_gcn_layer  : ps_linear with x2 = the importance pooling of h_full, pooled inside the tile (below, at the entry).
 //   ps_lsh_encode : codes = bitpack( x A^T >= 0 ), the random-hyperplane projection of
 //                   faiss.IndexLSH (reference utils/nearest_neighbors.py:26,43,66) with a wavefront
 //                   ballot bit-pack epilogue (LSB-first bytes, faiss fvec2bitvec).
@@ -25,6 +26,7 @@
 // the younger runs in its gaps; MFMA and VALU instructions do not overlap on a SIMD, which is what prices the epilogue
 // (tools/gemm_trace.py).
 #include "ps_common.h"
+#include "pool_row.h"
 #include <type_traits>
 
 #ifndef PS_GEMM_DEBUG
@@ -60,6 +62,11 @@ struct GemmArgs {
     float *y;            // EPI 0
     uint8_t *codes; int cs;  // EPI 1
     const int64_t *grp;      // optional (grouped products, psi_linear_grouped): per 64-row block (W row offset, columns, y offset)
+    // ps_gcn_layer (gemm_f32_kernel<..., GCN = PAGES>): rows in class order, the count of rows that keep a neighbour, the pooled-row
+    // slabs (64 x H per tile), and the pooling's operands (csrc/pool_row.h)
+    const int32_t *ord; const int32_t *nheavy; float *slab;
+    const float *hf; int H; const int32_t *ids; const int32_t *counts; const float *wts; const int32_t *nvalid; int T; int renorm;
+    int64_t max_idx;
 };
 
 // 8 consecutive k of one row (zero-filled outside [0,K) / invalid row)
@@ -155,8 +162,10 @@ __device__ __forceinline__ void stash_item_stored(float *d, f32x4 lo, f32x4 hi) 
 // fetch and the loads stay in flight under the MFMAs.  The general variant predicates every element.
 // The epilogue of a block tile (bias / ReLU / fused row L2 norm / stores, or the LSH sign + ballot bit-pack), shared by the one-tile
 // kernel and the persistent kernel below.  C layout (32x32 tile): col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).
-template <int WM, int WN, int TM, int TN, int EPI>
-__device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, f32x16 (&acc)[TM][TN], int64_t m0, int n0, float *sRed, float *sNrm) {
+// PERM (ps_gcn_layer): tile row rowl is output row sOrd[rowl].
+template <int WM, int WN, int TM, int TN, int EPI, bool PERM = false>
+__device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, f32x16 (&acc)[TM][TN], int64_t m0, int n0, float *sRed, float *sNrm,
+                                              const int *sOrd = nullptr) {
     constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NT = WM * WN * 64;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int wm = wv / WN, wn = wv % WN, li = lane & 31, lh = lane >> 5;
@@ -296,6 +305,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, f32x16 (&acc)[T
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 float *dst = g.y + (m0 + (wm * TM + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * g.N + n0 + wn * TN * 32 + li;
+                if constexpr (PERM) dst = g.y + (int64_t)sOrd[(wm * TM + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh] * g.N + n0 + wn * TN * 32 + li;
 #pragma unroll
                 for (int b = 0; b < TN; ++b) dst[b * 32] = acc[a][b][r];
             }
@@ -306,8 +316,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, f32x16 (&acc)[T
     for (int a = 0; a < TM; ++a)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int64_t row = m0 + (wm * TM + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            int64_t row = m0 + (wm * TM + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
             if (row >= g.M) continue;
+            if constexpr (PERM) row = sOrd[(wm * TM + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh];
 #pragma unroll
             for (int b = 0; b < TN; ++b) {
                 const int col = n0 + (wn * TN + b) * 32 + li;
@@ -317,7 +328,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, f32x16 (&acc)[T
     PS_TRACE(41);
 }
 
-template <int WM, int WN, int TM, int TN, int BK, int EPI, bool FAST>
+template <int WM, int WN, int TM, int TN, int BK, int EPI, bool FAST, int GCN = 0>
 #ifndef PS_GEMM_OCC
 #define PS_GEMM_OCC 2      // two blocks per CU (<= 256 VGPR + AGPR): one block's barriers and epilogue under the other's MFMAs
 #endif
@@ -330,8 +341,9 @@ __global__ __launch_bounds__(WM * WN * 64, PS_GEMM_OCC) void gemm_f32_kernel(Gem
     constexpr int GRP = BK / 8;                        // 8-k groups per row
     constexpr int LDS_STRIDE = BK + 4;                 // floats; 144 B (BK 32) / 80 B (BK 16): b128 reads conflict free
     constexpr int A_ITEMS = (BM * GRP + NT - 1) / NT, B_ITEMS = (BN * GRP + NT - 1) / NT;   // (row, group) items per thread
-    __shared__ __attribute__((aligned(16))) float smem[(BM + BN) * LDS_STRIDE + BM * WN + BM * 4];
+    __shared__ __attribute__((aligned(16))) float smem[(BM + BN) * LDS_STRIDE + BM * WN + BM * 4 + (GCN ? BM : 0)];
     float *sA = smem, *sB = smem + BM * LDS_STRIDE, *sRed = smem + (BM + BN) * LDS_STRIDE, *sNrm = sRed + BM * WN;
+    int *sOrd = reinterpret_cast<int *>(sNrm + BM * 4);
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int wm = wv / WN, wn = wv % WN;
@@ -357,6 +369,32 @@ __global__ __launch_bounds__(WM * WN * 64, PS_GEMM_OCC) void gemm_f32_kernel(Gem
     int trace_step = 0;
 #endif
     PS_TRACE(0);
+    // ps_gcn_layer: tile t holds rows ord[64 t .. 64 t + 63] (rows that keep a neighbour first).  A tile that holds one of them
+    // ("heavy") pools its 64 rows into its slab and contracts K + K2; any other tile contracts K only -- its pooled rows are +0.0, and
+    // fmaf(+0.0, w, acc) == acc for finite w except acc == -0.0, which the ReLU of the epilogue maps to +0.0 either way
+    int64_t xrow[A_ITEMS];
+    (void)xrow;
+    if constexpr (GCN > 0) {
+        static_assert(FAST && EPI == 0 && BM == 64 && NT == 256, "the 64-row tile of the layer GEMM");
+        const bool heavy = m0 < (int64_t)*g.nheavy;                              // block-uniform
+        if (tid < BM) sOrd[tid] = g.ord[m0 + tid < g.M ? m0 + tid : g.M - 1];
+        if (heavy) {
+            float *slab = g.slab + (int64_t)blockIdx.x * BM * g.H;
+#pragma unroll 1
+            for (int r0 = 0; r0 < BM; r0 += NT / 16) {                          // 16 rows per pass: four per wave
+                const int r = r0 + (tid >> 4);
+                const bool rok = m0 + r < g.M;
+                const int64_t i = rok ? (int64_t)g.ord[m0 + r] : 0;
+                pool4_row<GCN>(g.hf, g.H, g.ids, g.counts, g.wts, g.nvalid, i, rok, g.T, g.max_idx, g.renorm, slab + (int64_t)r * g.H);
+            }
+            g.x2 = slab;                                                         // read as tile rows 0..63 (below)
+        } else {
+            g.x2 = nullptr;
+        }
+        __syncthreads();                                                         // slab rows and sOrd written
+#pragma unroll
+        for (int q = 0; q < A_ITEMS; ++q) xrow[q] = sOrd[((tid + NT * q) % (BM * GRP)) / GRP];
+    }
     f32x16 acc[TM][TN];
 #pragma unroll
     for (int a = 0; a < TM; ++a)
@@ -385,7 +423,9 @@ __global__ __launch_bounds__(WM * WN * 64, PS_GEMM_OCC) void gemm_f32_kernel(Gem
                 const int it = FAST ? (tid + NT * q) % (BM * GRP) : tid + NT * q, row = it / GRP, grp = it % GRP;
                 const int64_t m = m0 + row;
                 if (FAST) {
-                    const float *src = X + (m < g.M ? m : g.M - 1) * K + k0 + grp * 8;
+                    int64_t srow = m < g.M ? m : g.M - 1;
+                    if constexpr (GCN > 0) srow = phase == 0 ? xrow[q] : srow - m0;     // x through the order; the slab by tile row
+                    const float *src = X + srow * K + k0 + grp * 8;
                     ra[q][0] = *reinterpret_cast<const f32x4 *>(src);
                     ra[q][1] = *reinterpret_cast<const f32x4 *>(src + 4);
                 } else if (it < BM * GRP) {
@@ -490,7 +530,7 @@ __global__ __launch_bounds__(WM * WN * 64, PS_GEMM_OCC) void gemm_f32_kernel(Gem
         }
     }
 
-    gemm_epilogue<WM, WN, TM, TN, EPI>(g, acc, m0, n0, sRed, sNrm);
+    gemm_epilogue<WM, WN, TM, TN, EPI, (GCN > 0)>(g, acc, m0, n0, sRed, sNrm, sOrd);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1220,6 +1260,146 @@ extern "C" int ps_linear(const float *x, int64_t M, int K, const float *W, int l
         hipLaunchKernelGGL(l2norm_rows_kernel, dim3((unsigned)grid), dim3(256), 0, st, y, M, N);
         PS_CHECK_LAUNCH();
     }
+    return PS_OK;
+}
+
+// ---- ps_gcn_layer ---------------------------------------------------------------------------------------------------------
+// One GraphSAGE layer, y = l2norm(relu(x W^T + pool(h_full) W2^T + b)), as three launches: gcn_count_kernel and gcn_order_kernel
+// sort the rows into two classes -- rows that keep at least one neighbour ("heavy") first, then the rest, each class in ascending
+// row order (a stable partition: per chunk a count, then per chunk the prefix of the counts and a block scan; no atomics, so the
+// order is the same on every run) -- and gemm_f32_kernel<1, 4, 2, 2, 32, 0, true, PAGES> runs the 64 x 256 tiles over the rows in
+// that order: a heavy tile pools its 64 rows (pool4_row, the same function as ps_importance_pool) into its slab of the workspace,
+// which stays in L2, and contracts K + K2; a tile of rows that keep nothing contracts K only.  The count of heavy rows stays on the
+// device.  At T = 10 on the catalogue graphs about half of the rows keep no item neighbour.
+namespace {
+
+constexpr int GCN_MAX_CHUNKS = 1024;
+
+int64_t gcn_chunk_rows(int64_t M) {
+    const int64_t c = ps_cdiv(ps_cdiv(M, GCN_MAX_CHUNKS), 256) * 256;
+    return c > 256 ? c : 256;
+}
+
+struct GcnWorkspace {
+    size_t slab, ord, cnt, total;
+};
+GcnWorkspace gcn_workspace(int64_t M, int H) {
+    GcnWorkspace w;
+    w.slab = 0;
+    w.ord = (size_t)ps_cdiv(M, 64) * 64 * (size_t)H * sizeof(float);
+    w.cnt = w.ord + (size_t)ps_cdiv(M, 64) * 64 * sizeof(int32_t);
+    w.total = w.cnt + (GCN_MAX_CHUNKS + 64) * sizeof(int32_t);      // chunk counts, then the heavy-row count
+    return w;
+}
+
+__global__ __launch_bounds__(256) void gcn_count_kernel(const int32_t *__restrict__ ids, const int32_t *__restrict__ nvalid, int64_t M,
+                                                        int T, int64_t max_idx, int64_t chunk, int32_t *__restrict__ cnt) {
+    __shared__ int sw[4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * chunk, r1 = r0 + chunk < M ? r0 + chunk : M;
+    int c = 0;
+    for (int64_t i = r0 + tid; i < r1; i += 256) c += pool_row_keeps(ids, nvalid, i, T, max_idx) ? 1 : 0;
+    c = ps_wave_sum_i32(c);
+    if (lane == 0) sw[wv] = c;
+    __syncthreads();
+    if (tid == 0) cnt[blockIdx.x] = sw[0] + sw[1] + sw[2] + sw[3];
+}
+
+__global__ __launch_bounds__(256) void gcn_order_kernel(const int32_t *__restrict__ ids, const int32_t *__restrict__ nvalid, int64_t M,
+                                                        int T, int64_t max_idx, int64_t chunk, int nchunks,
+                                                        const int32_t *__restrict__ cnt, int32_t *__restrict__ ord,
+                                                        int32_t *__restrict__ nheavy) {
+    __shared__ int sb[4], st[4], sh[4], se[4];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int64_t r0 = (int64_t)blockIdx.x * chunk, r1 = r0 + chunk < M ? r0 + chunk : M;
+    // heavy rows of the chunks before this one, and of all chunks
+    int before = 0, total = 0;
+    for (int j = tid; j < nchunks; j += 256) {
+        const int v = cnt[j];
+        total += v;
+        before += j < (int)blockIdx.x ? v : 0;
+    }
+    before = ps_wave_sum_i32(before);
+    total = ps_wave_sum_i32(total);
+    if (lane == 0) { sb[wv] = before; st[wv] = total; }
+    __syncthreads();
+    before = sb[0] + sb[1] + sb[2] + sb[3];
+    total = st[0] + st[1] + st[2] + st[3];
+    if (blockIdx.x == 0 && tid == 0) *nheavy = total;
+    int64_t hoff = before, eoff = total + (r0 - before);     // next slot of each class
+    for (int64_t base = r0; base < r1; base += 256) {
+        const int64_t i = base + tid;
+        const bool in = i < r1;
+        const bool f = in && pool_row_keeps(ids, nvalid, i, T, max_idx);
+        const uint64_t hm = __ballot(f), em = __ballot(in && !f);
+        const int hr = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
+        const int er = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(em >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)em, 0u));
+        if (lane == 0) { sh[wv] = __popcll(hm); se[wv] = __popcll(em); }
+        __syncthreads();
+        int hb = 0, eb = 0, ht = 0, et = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            hb += w < wv ? sh[w] : 0;
+            eb += w < wv ? se[w] : 0;
+            ht += sh[w];
+            et += se[w];
+        }
+        if (in) ord[f ? hoff + hb + hr : eoff + eb + er] = (int32_t)i;
+        hoff += ht;
+        eoff += et;
+        __syncthreads();                                     // sh / se are rewritten by the next pass
+    }
+}
+
+bool env_set(const char *name) {
+    const char *e = getenv(name);
+    return e != nullptr && *e != '\0';
+}
+
+}  // namespace
+
+extern "C" size_t ps_gcn_layer_workspace_bytes(int64_t M, int H) {
+    if (M <= 0 || H <= 0) return 0;
+    return gcn_workspace(M, H).total;
+}
+
+extern "C" int ps_gcn_layer(const float *x, int64_t M, int K, const float *W, int ldw, const float *b, int N, const float *h_full,
+                            int64_t n_full, int H, const int32_t *ids, const int32_t *counts, const float *wts, const int32_t *nvalid,
+                            int T, int64_t max_idx, int renorm, const float *W2, int ldw2, int flags, float *y, void *workspace,
+                            size_t workspace_bytes, ps_stream_t stream) {
+    if (M < 0 || K <= 0 || N <= 0 || ldw < K || H <= 0 || ldw2 < H || T <= 0 || n_full < 0) return PS_EINVAL;
+    if (flags & ~(PS_RELU | PS_L2NORM | PS_WPERM)) return PS_EINVAL;
+    if (M > 0 && (!x || !W || !y || !h_full || !W2 || !ids || !nvalid || (!counts && !wts))) return PS_EINVAL;
+    // the shapes of gemm_f32_kernel<1, 4, 2, 2, 32, 0, true> (ps_linear's layer GEMM of many rows); every other one -- and
+    // PS_GCN_FUSED=0, or an experiment switch of the separate kernels -- is the caller's ps_importance_pool + ps_linear
+    const char *fe = getenv("PS_GCN_FUSED");
+    const char *se = getenv("PS_GEMM_SHARD"), *pe = getenv("PS_POOL_ROWS_PER_WAVE");
+    if ((fe && atoi(fe) == 0) || (se && atoi(se) > 0) || env_set("PS_GEMM_DMA") || (pe && atoi(pe) == 1)) return PS_EUNSUPPORTED;
+    // T <= 16 only: at T = 50 (BASELINE config 3) every row keeps a neighbour, nothing is skipped, and pooling 50 entries in the
+    // tile's prologue measured slower than the separate launch (config 3 step 1.56 -> 1.64 ms); at T = 10 the step gains 60-80 us
+    if (N != 256 || (flags & (PS_RELU | PS_L2NORM)) != (PS_RELU | PS_L2NORM) || M < 64 * 384 || M > 0x7fffffff - 64 || T > 16)
+        return PS_EUNSUPPORTED;
+    if (!aligned_operand(x, K, K) || !aligned_operand(W, K, ldw) || !aligned_operand(W2, H, ldw2) || !aligned_operand(h_full, H, H))
+        return PS_EUNSUPPORTED;
+    const GcnWorkspace wl = gcn_workspace(M, H);
+    if (!workspace || workspace_bytes < wl.total || reinterpret_cast<size_t>(workspace) % 16 != 0) return PS_EWORKSPACE;
+    if (max_idx > n_full - 1) max_idx = n_full - 1;
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    int32_t *ord = reinterpret_cast<int32_t *>(ws + wl.ord), *cnt = reinterpret_cast<int32_t *>(ws + wl.cnt);
+    int32_t *nheavy = cnt + GCN_MAX_CHUNKS;
+    hipStream_t st = ps_stream(stream);
+    const int64_t chunk = gcn_chunk_rows(M);
+    const int nchunks = (int)ps_cdiv(M, chunk);
+    hipLaunchKernelGGL(gcn_count_kernel, dim3((unsigned)nchunks), dim3(256), 0, st, ids, nvalid, M, T, max_idx, chunk, cnt);
+    PS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(gcn_order_kernel, dim3((unsigned)nchunks), dim3(256), 0, st, ids, nvalid, M, T, max_idx, chunk, nchunks, cnt, ord,
+                       nheavy);
+    PS_CHECK_LAUNCH();
+    GemmArgs g{x, M, K, W, ldw, nullptr, H, W2, ldw2, b, N, flags, y, nullptr, 0, nullptr,
+               ord, nheavy, reinterpret_cast<float *>(ws + wl.slab), h_full, H, ids, counts, wts, nvalid, T, renorm, max_idx};
+    const dim3 grid((unsigned)ps_cdiv(M, 64), 1);
+    hipLaunchKernelGGL((gemm_f32_kernel<1, 4, 2, 2, 32, 0, true, 1>), grid, dim3(256), 0, st, g);
+    PS_CHECK_LAUNCH();
     return PS_OK;
 }
 

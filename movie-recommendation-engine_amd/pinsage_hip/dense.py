@@ -99,6 +99,53 @@ def linear(x, W, b=None, x2=None, W2=None, relu=False, l2norm=False):
     return y
 
 
+def gcn_layer(x, W, b, h_full, ids, counts, nvalid, W2, wts=None, max_idx=None, renorm=True, relu=True, l2norm=True):
+    """linear(x, W, b, x2=importance_pool(h_full, ids, counts, wts, nvalid, max_idx, renorm), W2=W2, relu, l2norm) -- the same
+    bits -- in one launch where ps_gcn_layer serves the shape (rows that keep no neighbour skip the W2 half, the pooled rows are
+    not written out); elsewhere, and under PS_GCN_FUSED=0, as that pair of calls.  W / W2: matrices or StagedWeights (both or
+    neither)."""
+    from . import sampling
+    staged = isinstance(W, StagedWeight)
+    if isinstance(W2, StagedWeight) != staged:
+        raise ValueError("W and W2 must both be staged or both plain")
+    Wm, W2m = (W.t, W2.t) if staged else (W, W2)
+    _require_cuda(x, Wm, b, h_full, W2m, ids, counts, wts, nvalid)
+    x, h_full = x.contiguous(), h_full.contiguous()
+    if x.dtype != torch.float32 or h_full.dtype != torch.float32:
+        raise TypeError("fp32 expected")
+    M, K = int(x.size(0)), int(x.size(1))
+    n_full, H = int(h_full.size(0)), int(h_full.size(1))
+    Wk, ldw = _rowmajor(Wm)
+    W2k, ldw2 = _rowmajor(W2m)
+    N = int(Wk.size(0))
+    if int(Wk.size(1)) != K or int(W2k.size(1)) != H or int(W2k.size(0)) != N or int(ids.size(0)) != M:
+        raise ValueError("shape mismatch")
+    T = int(ids.size(1))
+    if max_idx is None:
+        max_idx = n_full - 1
+    if b is not None:
+        b = b.contiguous()
+    ids, nvalid = ids.contiguous(), nvalid.contiguous()
+    counts = counts.contiguous() if counts is not None else None
+    wts = wts.contiguous() if wts is not None else None
+    flags = (nv.PS_RELU if relu else 0) | (nv.PS_L2NORM if l2norm else 0) | (nv.PS_WPERM if staged else 0)
+    L = nv.lib()
+    wsb = int(L.ps_gcn_layer_workspace_bytes(nv.i64(M), nv.i32(H)))
+    if wsb > 0:
+        y = torch.empty((M, N), dtype=torch.float32, device=x.device)
+        ws = torch.empty((wsb,), dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            rc = L.ps_gcn_layer(nv.ptr(x), nv.i64(M), nv.i32(K), _ptr_view(Wk), nv.i32(ldw), nv.ptr(b), nv.i32(N), nv.ptr(h_full),
+                                nv.i64(n_full), nv.i32(H), nv.ptr(ids), nv.ptr(counts), nv.ptr(wts), nv.ptr(nvalid), nv.i32(T),
+                                nv.i64(int(max_idx)), nv.i32(int(renorm)), _ptr_view(W2k), nv.i32(ldw2), nv.i32(flags), nv.ptr(y),
+                                nv.ptr(ws), nv.C.c_size_t(wsb), nv.stream())
+        if rc != nv.PS_EUNSUPPORTED:
+            nv.check(rc, "ps_gcn_layer")
+            return y
+    h_neigh = sampling.importance_pool(h_full, ids=ids, counts=counts, wts=wts, nvalid=nvalid, max_idx=max_idx, renorm=renorm)
+    return linear(x, W, b, x2=h_neigh, W2=W2, relu=relu, l2norm=l2norm)
+
+
 def lsh_encode(x, A):
     """codes uint8[n, nbits/8]: bit j = (x . A[j] >= 0), LSB first (faiss IndexLSH.sa_encode).  A: matrix or StagedWeight."""
     staged = isinstance(A, StagedWeight)

@@ -162,6 +162,10 @@ class HipOps:
     def linear(self, x, W, b, x2=None, W2=None, relu=False, l2norm=False):
         return dense.linear(x, W, b, x2=x2, W2=W2, relu=relu, l2norm=l2norm)
 
+    def gcn_layer(self, x, W, b, h_full, batch, max_idx, W2):
+        """linear(x, W, b, x2=pool(h_full, batch, max_idx), W2=W2, relu=True, l2norm=True) in one launch (ps_gcn_layer)"""
+        return dense.gcn_layer(x, W, b, h_full, batch.ids, batch.counts, batch.nvalid, W2, max_idx=max_idx)
+
     def lsh_encode(self, x, A):
         return dense.lsh_encode(x, A)
 
@@ -319,8 +323,11 @@ class ShardedPinSage:
             h_full = pending.wait()                                          # the per-layer exchange
             if side is not None:
                 torch.cuda.current_stream(dev).wait_event(ready[i])
-            h_neigh = ops.pool(h_full, batches[i], self.M - 1)
-            h = ops.linear(a_in, self._w(("l1", i), W1), b1, x2=h_neigh, W2=self._w(("l2", i), Wu[:, H:]), relu=True, l2norm=True)
+            if self.fuse_self and hasattr(ops, "gcn_layer"):                  # pooling inside the layer GEMM
+                h = ops.gcn_layer(a_in, self._w(("l1", i), W1), b1, h_full, batches[i], self.M - 1, self._w(("l2", i), Wu[:, H:]))
+            else:
+                h_neigh = ops.pool(h_full, batches[i], self.M - 1)
+                h = ops.linear(a_in, self._w(("l1", i), W1), b1, x2=h_neigh, W2=self._w(("l2", i), Wu[:, H:]), relu=True, l2norm=True)
             if i + 1 < self.num_layers:
                 pending = self.comm.gather_rows_async(h, self.chunk, "h")
         return ops.linear(h, self._w("out", P["output_proj.weight"]), P["output_proj.bias"], l2norm=True)
