@@ -291,6 +291,22 @@ size_t ps_dot_topk_workspace_bytes(int64_t nq, int64_t N, int D, int k);
 int ps_dot_topk(const float *E, int64_t N, int D, const int64_t *qidx, int64_t nq, int k, int exclude_self,
                 float *vals, int64_t *ids, void *workspace, size_t workspace_bytes, ps_stream_t stream);
 
+/* ---- the rank of a target item (utils/evaluation.py:5-102: hit rate @ k, MRR) --------------------------------------------
+ * ps_row_dot    : out[i] = A[ia[i]] . B[ib[i]], out float[n]; the arithmetic of ps_linear / ps_dot_topk (one fmaf chain, k
+ *                 ascending, from +0.0), so out[i] is bit-identical to that GEMM's entry for the pair.  An index outside
+ *                 [0, nA) / [0, nB) gives NaN (nothing is read).
+ * ps_rank_count : E float[N,D] (the items with ids id_offset .. id_offset + N - 1), Q float[nq,D], thr float[nq], tid int64[nq]:
+ *                   count[i] += #{ j in [0,N) : Q_i . E_j precedes thr[i] in ps_dot_topk's order, or equals it (same key)
+ *                                               with id_offset + j < tid[i] }
+ *                 ps_dot_topk's order: similarity descending by the key of its float bits (+0.0 before -0.0, NaN by bits),
+ *                 ties by ascending id.  With thr[i] = ps_row_dot(Q_i, E_t) and tid[i] = t, rank = count + 1.  count int64[nq]
+ *                 is ADDED to, not written: calls over disjoint item ranges (id_offset) sum to the count of their union.
+ *                 One GEMM with a counting epilogue (no [nq, N] slab); N < 2^31. */
+int ps_row_dot(const float *A, int64_t nA, const float *B, int64_t nB, int D, const int64_t *ia, const int64_t *ib, int64_t n,
+               float *out, ps_stream_t stream);
+int ps_rank_count(const float *E, int64_t N, int D, int64_t id_offset, const float *Q, int64_t nq, const float *thr,
+                  const int64_t *tid, int64_t *count, ps_stream_t stream);
+
 /* ---- next row: exact L2 / IVF search behind WeakANDIndex and benchmark_search_methods
  * (utils/nearest_neighbors.py:70-139, 176: faiss.IndexFlatL2 / faiss.IndexIVFFlat).
  * dist(q, x) = |q|^2 + |x|^2 - 2 q.x in fp32; k smallest by (distance, id), ascending; dist float[nq,k]

@@ -67,6 +67,8 @@ struct GemmArgs {
     const int32_t *ord; const int32_t *nheavy; float *slab;
     const float *hf; int H; const int32_t *ids; const int32_t *counts; const float *wts; const int32_t *nvalid; int T; int renorm;
     int64_t max_idx;
+    // EPI 2 (ps_rank_count): per row the target's similarity and id, the id of column 0, the counts (+=)
+    const float *thr; const int64_t *tgt; int64_t id_off; int64_t *cnt;
 };
 
 // 8 consecutive k of one row (zero-filled outside [0,K) / invalid row)
@@ -84,6 +86,7 @@ __device__ __forceinline__ void load8(const float *base, bool row_ok, int k, int
 // Sum over the 32 lanes of each wave half, valid in lanes 16..31 / 48..63, with DPP only (gemm_dma_kernel)
 #define PS_DPP_ACC(v, ctrl, rows) \
     (v) += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (v)), (ctrl), (rows), 0xf, true))
+#define PS_DPP_ACC_U(v, ctrl, rows) (v) += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), (ctrl), (rows), 0xf, true)
 __device__ __forceinline__ float half_sum32(float v) {
     PS_DPP_ACC(v, 0xB1, 0xf);    // quad_perm [1,0,3,2]: lane ^ 1
     PS_DPP_ACC(v, 0x4E, 0xf);    // quad_perm [2,3,0,1]: lane ^ 2
@@ -92,7 +95,23 @@ __device__ __forceinline__ float half_sum32(float v) {
     PS_DPP_ACC(v, 0x142, 0xa);   // row_bcast:15 -> rows 1 and 3 add the row before them
     return v;
 }
+__device__ __forceinline__ uint32_t half_sum32_u32(uint32_t v) {      // the same sum on integers (ps_rank_count's packed counts)
+    PS_DPP_ACC_U(v, 0xB1, 0xf);
+    PS_DPP_ACC_U(v, 0x4E, 0xf);
+    PS_DPP_ACC_U(v, 0x141, 0xf);
+    PS_DPP_ACC_U(v, 0x140, 0xf);
+    PS_DPP_ACC_U(v, 0x142, 0xa);
+    return v;
+}
 #undef PS_DPP_ACC
+#undef PS_DPP_ACC_U
+
+// Order key of a similarity for ps_rank_count: signed and increasing in the float's total order (-NaN < -inf < ... < -0 < +0 <
+// ... < +inf < +NaN), i.e. desc_key of csrc/dot_topk.hip minus 2^31 and reversed: key(a) > key(b) <=> desc_key(a) < desc_key(b)
+__device__ __forceinline__ int32_t rank_key(float v) {
+    const int32_t b = __float_as_int(v);
+    return b ^ ((b >> 31) & 0x7fffffff);
+}
 
 // Row sums of the fused L2 norm.  Every lane holds NV partial sums (one per row of its wave tile: v[idx], idx = 16 a + r)
 // over ITS column; wanted: the sums over the 32 columns of the lane's wave half.  Reducing every value over 32 lanes takes
@@ -173,6 +192,54 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, f32x16 (&acc)[T
     PS_TRACE(40);
     // ------------------------------ epilogue -------------------------------------------------
     // C layout (32x32 tile): col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
+    if constexpr (EPI == 2) {
+        // ps_rank_count: the columns that precede the row's target in (similarity descending, id ascending) order.  A lane holds
+        // TN columns of 16 rows per 32-row tile; its counts (<= TN) go into the bytes of four words (word r >> 2, byte r & 3: rows
+        // 8 (r >> 2) + 4 lh + 0..3), the 32 lanes of a wave half add the words (<= 32 TN per byte: no carry), the WN column waves
+        // meet in LDS, and one thread per row adds the block's count to the row's total: one 64-bit atomic add per (row, block
+        // tile), 64 consecutive rows per wave instruction, none for a row the block counted 0 for.  No [M, N] slab is written.
+        static_assert(32 * TN < 256 && BM <= NT, "byte-packed counts, one thread per row");
+        int32_t *sCnt = reinterpret_cast<int32_t *>(sRed);                      // [BM][WN]
+        bool colok[TN];
+#pragma unroll
+        for (int b = 0; b < TN; ++b) colok[b] = n0 + (wn * TN + b) * 32 + li < g.N;
+#pragma unroll
+        for (int a = 0; a < TM; ++a) {
+            uint32_t pk[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                int64_t row = m0 + (wm * TM + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                row = row < g.M ? row : g.M - 1;                                 // rows past the end are counted, never added
+                const int32_t kt = rank_key(g.thr[row]);
+                const int64_t lim = g.tgt[row] - g.id_off;                       // columns whose id is below the target's
+                const int cl = lim < 0 ? 0 : lim > g.N ? g.N : (int)lim;
+                uint32_t c = 0;
+#pragma unroll
+                for (int b = 0; b < TN; ++b) {
+                    const int col = n0 + (wn * TN + b) * 32 + li;
+                    const int32_t kv = rank_key(acc[a][b][r]);
+                    c += (colok[b] && (kv > kt || (kv == kt && col < cl))) ? 1u : 0u;
+                }
+                pk[r >> 2] |= c << (8 * (r & 3));
+            }
+#pragma unroll
+            for (int w = 0; w < 4; ++w) pk[w] = half_sum32_u32(pk[w]);        // complete in lanes 16..31 of each half
+            if (li >= 16) {
+                const int r = li - 16;
+                const uint32_t word = r < 4 ? pk[0] : r < 8 ? pk[1] : r < 12 ? pk[2] : pk[3];
+                sCnt[((wm * TM + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh) * WN + wn] = (int32_t)((word >> (8 * (r & 3))) & 0xffu);
+            }
+        }
+        __syncthreads();
+        if (tid < BM) {
+            int32_t t = 0;
+#pragma unroll
+            for (int w = 0; w < WN; ++w) t += sCnt[tid * WN + w];
+            if (m0 + tid < g.M && t != 0) atomicAdd(reinterpret_cast<unsigned long long *>(g.cnt + m0 + tid), (unsigned long long)t);
+        }
+        PS_TRACE(41);
+        return;
+    }
     if (EPI == 1) {
         uint32_t *codes32 = reinterpret_cast<uint32_t *>(g.codes);
         const int words = g.cs >> 2;
@@ -1435,4 +1502,78 @@ extern "C" int ps_lsh_encode(const float *x, int64_t N, int D, const float *A, i
     if (!x || !A || !codes || reinterpret_cast<size_t>(codes) % 4 != 0) return PS_EINVAL;
     GemmArgs g{x, N, D, A, D, nullptr, 0, nullptr, 0, nullptr, nbits, flags, nullptr, codes, nbits / 8};
     return launch_gemm<1>(g, ps_stream(stream));
+}
+
+// ---- ps_row_dot / ps_rank_count: the rank of a target item in a query's similarity order ------------------------------------
+// thr = ps_row_dot(Q row, target row) is the very entry the GEMM computes for that (query, item): one fmaf chain, k ascending,
+// from +0.0.  ps_rank_count runs ps_linear's tiles with the EPI 2 epilogue above: it compares every accumulator with its row's
+// threshold and keeps counts only.
+namespace {
+
+__global__ void row_dot_kernel(const float *__restrict__ A, int64_t nA, const float *__restrict__ B, int64_t nB, int D,
+                               const int64_t *__restrict__ ia, const int64_t *__restrict__ ib, int64_t n, float *__restrict__ out) {
+    const bool vec = D % 4 == 0 && reinterpret_cast<size_t>(A) % 16 == 0 && reinterpret_cast<size_t>(B) % 16 == 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t a = ia[i], b = ib[i];
+        if (a < 0 || a >= nA || b < 0 || b >= nB) {               // never read outside the matrices
+            out[i] = __builtin_nanf("");
+            continue;
+        }
+        const float *x = A + a * D, *y = B + b * D;
+        float s = 0.f;
+        if (vec) {
+            for (int k = 0; k < D; k += 4) {
+                const float4 u = *reinterpret_cast<const float4 *>(x + k), v = *reinterpret_cast<const float4 *>(y + k);
+                s = fmaf(u.x, v.x, s);
+                s = fmaf(u.y, v.y, s);
+                s = fmaf(u.z, v.z, s);
+                s = fmaf(u.w, v.w, s);
+            }
+        } else {
+            for (int k = 0; k < D; ++k) s = fmaf(x[k], y[k], s);
+        }
+        out[i] = s;
+    }
+}
+
+// the tiles of a plain ps_linear of the same shape (launch_gemm_v without the fused norm): persistent 64 x 128 tiles for aligned
+// operands, the one-tile kernel otherwise
+template <bool FAST>
+int launch_rank(const GemmArgs &g, hipStream_t st) {
+    if (FAST && g.N > 128) return launch_persistent<2, 2, 1, 2, 2>(g, st);
+    const int64_t tiles_n = ps_cdiv(g.N, 128);
+    if (tiles_n > 65535) return PS_EUNSUPPORTED;
+    dim3 grid((unsigned)ps_cdiv(g.M, 64), (unsigned)tiles_n);
+    hipLaunchKernelGGL((gemm_f32_kernel<2, 2, 1, 2, 32, 2, FAST>), grid, dim3(256), 0, st, g);
+    PS_CHECK_LAUNCH();
+    return PS_OK;
+}
+
+}  // namespace
+
+extern "C" int ps_row_dot(const float *A, int64_t nA, const float *B, int64_t nB, int D, const int64_t *ia, const int64_t *ib,
+                          int64_t n, float *out, ps_stream_t stream) {
+    if (nA < 0 || nB < 0 || D <= 0 || n < 0) return PS_EINVAL;
+    if (n == 0) return PS_OK;
+    if (!A || !B || !ia || !ib || !out) return PS_EINVAL;
+    int64_t grid = ps_cdiv(n, 256);
+    if (grid > 4096) grid = 4096;
+    hipLaunchKernelGGL(row_dot_kernel, dim3((unsigned)grid), dim3(256), 0, ps_stream(stream), A, nA, B, nB, D, ia, ib, n, out);
+    PS_CHECK_LAUNCH();
+    return PS_OK;
+}
+
+extern "C" int ps_rank_count(const float *E, int64_t N, int D, int64_t id_offset, const float *Q, int64_t nq, const float *thr,
+                             const int64_t *tid, int64_t *count, ps_stream_t stream) {
+    if (N < 0 || D <= 0 || nq < 0) return PS_EINVAL;
+    if (N > 0x7fffffff || nq > (int64_t)0x7fffffff * 64) return PS_EUNSUPPORTED;
+    if (N == 0 || nq == 0) return PS_OK;
+    if (!E || !Q || !thr || !tid || !count || reinterpret_cast<size_t>(count) % 8 != 0) return PS_EINVAL;
+    GemmArgs g{Q, nq, D, E, D, nullptr, 0, nullptr, 0, nullptr, (int)N, 0, nullptr, nullptr, 0};
+    g.thr = thr;
+    g.tgt = tid;
+    g.id_off = id_offset;
+    g.cnt = count;
+    hipStream_t st = ps_stream(stream);
+    return aligned_operand(Q, D, D) && aligned_operand(E, D, D) ? launch_rank<true>(g, st) : launch_rank<false>(g, st);
 }

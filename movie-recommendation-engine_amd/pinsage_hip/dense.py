@@ -312,6 +312,72 @@ def dot_topk(E, qidx, k, exclude_self=True):
     return vals, ids
 
 
+def _fp32_rows(E):
+    _require_cuda(E)
+    if E.dtype != torch.float32 or E.dim() != 2:
+        raise TypeError("fp32 [N, D] matrix expected")
+    return E.contiguous()
+
+
+def row_dot(A, ia, B, ib):
+    """out[i] = A[ia[i]] . B[ib[i]] (ps_row_dot): the arithmetic of linear() / dot_topk(), so out[i] is bit-identical to the
+    entry linear(A[ia], B)[i, ib[i]].  An index outside the matrix gives NaN."""
+    A, B = _fp32_rows(A), _fp32_rows(B)
+    if int(A.size(1)) != int(B.size(1)):
+        raise ValueError(f"shape mismatch: A {tuple(A.shape)} vs B {tuple(B.shape)}")
+    ia = ia.to(device=A.device, dtype=torch.int64).contiguous()
+    ib = ib.to(device=A.device, dtype=torch.int64).contiguous()
+    if ia.numel() != ib.numel():
+        raise ValueError("ia and ib must have the same length")
+    out = torch.empty(int(ia.numel()), dtype=torch.float32, device=A.device)
+    with torch.cuda.device(A.device):
+        nv.call("ps_row_dot", nv.ptr(A), nv.i64(int(A.size(0))), nv.ptr(B), nv.i64(int(B.size(0))), nv.i32(int(A.size(1))),
+                nv.ptr(ia), nv.ptr(ib), nv.i64(int(ia.numel())), nv.ptr(out), nv.stream())
+    return out
+
+
+def rank_count(E, Q, thr, tid, id_offset=0, count=None):
+    """count[i] += #{items j of E (ids id_offset + j) that precede (thr[i], tid[i]) in dot_topk's order of Q[i] . E^T}
+    (ps_rank_count: similarity descending by float key, ties by ascending id).  One GEMM with a counting epilogue, no [nq, N]
+    slab.  count: int64 [nq] on the device (a new zero vector when None); calls over disjoint item ranges add up."""
+    E, Q = _fp32_rows(E), _fp32_rows(Q)
+    if int(E.size(1)) != int(Q.size(1)):
+        raise ValueError(f"shape mismatch: E {tuple(E.shape)} vs Q {tuple(Q.shape)}")
+    nq = int(Q.size(0))
+    thr = thr.to(device=Q.device, dtype=torch.float32).contiguous()
+    tid = tid.to(device=Q.device, dtype=torch.int64).contiguous()
+    if int(thr.numel()) != nq or int(tid.numel()) != nq:
+        raise ValueError("thr and tid need one entry per query row")
+    if count is None:
+        count = torch.zeros(nq, dtype=torch.int64, device=Q.device)
+    elif count.dtype != torch.int64 or not count.is_contiguous() or int(count.numel()) != nq or count.device != Q.device:
+        raise ValueError("count must be a contiguous int64 [nq] tensor on the queries' device")
+    with torch.cuda.device(Q.device):
+        nv.call("ps_rank_count", nv.ptr(E), nv.i64(int(E.size(0))), nv.i32(int(E.size(1))), nv.i64(int(id_offset)), nv.ptr(Q),
+                nv.i64(nq), nv.ptr(thr), nv.ptr(tid), nv.ptr(count), nv.stream())
+    return count
+
+
+def target_rank(E, qidx, gt, id_offset=0):
+    """1-based rank of item gt[i] in the similarity order of query row qidx[i] over all rows of E (dot_topk's order:
+    similarity descending, ties by ascending id), int64 on the device.  qidx / gt are row indices of E in [0, N); E's row j
+    has the id id_offset + j (ties compare those ids, so the ranks do not depend on it -- the offset matters to rank_count
+    over item ranges).  rank <= k  <=>  gt[i] is in dot_topk(E, qidx, k, exclude_self=False)[1][i]."""
+    E = _fp32_rows(E)
+    qidx = qidx.to(device=E.device, dtype=torch.int64).contiguous()
+    gt = gt.to(device=E.device, dtype=torch.int64).contiguous()
+    if qidx.numel() != gt.numel():
+        raise ValueError("qidx and gt must have the same length")
+    N = int(E.size(0))
+    for name, t in (("qidx", qidx), ("gt", gt)):
+        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= N):
+            raise IndexError(f"{name} holds a row index outside [0, {N})")
+    Q = E.index_select(0, qidx)
+    thr = row_dot(E, qidx, E, gt)
+    count = rank_count(E, Q, thr, gt + int(id_offset), id_offset)
+    return count + 1
+
+
 def l2_topk(X, Q, k, assign=None, probe=None):
     """k nearest by squared L2 (IndexFlatL2 / IndexIVFFlat scan): -> (dist fp32[nq,k], ids int64[nq,k])."""
     X = X.contiguous()
