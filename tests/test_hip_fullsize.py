@@ -26,11 +26,20 @@ def big():
 
 @pytest.fixture(scope="module")
 def host_graph(big):
-    """host copy of the device-built CSR + CDF for the C oracle (the build itself is held to the oracle's by
-    test_hip_sampler.py::test_csr_cdf_bit_exact_vs_oracle and, below, on the heaviest rows)"""
+    """the C oracle's own CSR + CDF, built from the host copy of the edge list (not from the device's arrays), and asserted
+    bit-equal to the device build: 50 M edges, the 81 K-edge item row, every grid-stride loop of csr_build.hip"""
+    import time
     from oracle import c_oracle as co
-    g = big[0]
-    return co.Graph.from_arrays(g.rowptr.cpu().numpy(), g.col.cpu().numpy(), g.cdf.cpu().numpy())
+    g, ei, ew = big
+    t0 = time.time()
+    cg = co.Graph(ei.cpu().numpy(), ew.cpu().numpy(), threads=_oracle_threads())
+    print(f"oracle graph build ({cg.E} edges): {time.time() - t0:.1f} s", flush=True)
+    assert cg.V == g.V and cg.E == g.E
+    assert np.array_equal(cg.rowptr, g.rowptr.cpu().numpy())
+    assert np.array_equal(cg.col, g.col.cpu().numpy())
+    assert np.array_equal(cg.cdf.view(np.int64), g.cdf.cpu().numpy().view(np.int64))
+    assert int(np.diff(cg.rowptr)[:59047].max()) > 65536                    # the heaviest item row (~81 K edges) is in there
+    return cg
 
 
 def _oracle_threads():
@@ -140,6 +149,29 @@ def test_graph_invariants_full_size(big):
     assert bool((start >= lo).all()) and bool((start < g.rowptr[row + 1]).all())
     prev_ok = (start == lo) | (g.cdf[(start - 1).clamp(min=0)] <= t)
     assert bool(prev_ok.all())
+
+
+def test_lookup_records_full_size_match_their_definitions(big):
+    """Node records, guide, packed blocks, both bucket record forms and the destination records of SYN-25M against their
+    definitions, every edge (tests/helpers/graph_defs.py): the default graph holds the 32-byte half records; a second build
+    forces the 64-byte records and the destination records, whose kernel is a grid-stride loop of 65 536 x 256 threads that
+    takes a third pass over 50 M edges."""
+    import sys
+    from pinsage_hip.graph import DeviceGraph
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+    from graph_defs import check_graph_definitions
+    g, ei, ew = big
+    assert g.bucket_bytes == 32 and g.E > 2 * 65536 * 256
+    gf = DeviceGraph(ei, ew, buckets="full", dest_info=True)
+    assert gf.bucket_bytes == 64 and gf.dest_info is not None
+    assert torch.equal(gf.rowptr, g.rowptr) and torch.equal(gf.col, g.col) and torch.equal(gf.cdf, g.cdf)
+    check_graph_definitions(gf)
+    del gf
+    # the module's graph itself: checked on copies of its arrays (check_graph_definitions compacts / expands the graph)
+    gh = DeviceGraph.__new__(DeviceGraph)
+    gh.__dict__.update(g.__dict__)
+    check_graph_definitions(gh)
+    torch.cuda.empty_cache()
 
 
 @pytest.mark.parametrize("T", [10, 50])                            # BASELINE configs 2 / 3

@@ -470,6 +470,49 @@ def test_spmm_csr_matches_scatter_add(H, weights):
     np.testing.assert_allclose(out.numpy(), ref.numpy(), rtol=1e-5, atol=1e-4 if H == 32 else 2e-4)
 
 
+@pytest.mark.parametrize("H,x_offset", [(512, 0), (300, 0), (130, 0), (256, 1)])
+def test_spmm_csr_column_passes_and_large_target_csr(H, x_offset):
+    """ps_spmm_csr's column loop (c0 += 64 VEC) past its first pass: H = 512 (VEC 4, two passes), 300 (VEC 4, a partial second
+    pass), 130 (VEC 1: H % 4 != 0, three passes), 256 with x one float off a 16-byte boundary (a contiguous view: VEC 1, four
+    passes).  ~300 K edges (> 65 536: TargetCSR.perm's high 16 bits, carried by its second ps_csr_build, are not all zero).
+    Rows: empty, exactly 512 edges on a slice boundary (stored whole), 513 (cut), a ~100 K-edge hub over ~200 atomic slices.
+    Reference: fp64 index_add_; each element within 2^-20 of its accumulated magnitude sum |w x|."""
+    from pinsage_hip import graph as G
+    rng = np.random.default_rng(9)
+    V = 4000
+    deg = rng.integers(20, 80, V)
+    deg[5] = 0
+    deg[1000] = 100_000
+    deg[2000], deg[2001] = 512, 513
+    deg[1999] += (-int(deg[:2000].sum())) % 512                            # row 2000 starts on a 512-edge slice
+    assert deg[:2000].sum() % 512 == 0
+    dst = np.repeat(np.arange(V), deg)
+    E = dst.size
+    p = rng.permutation(E)
+    dst = dst[p]
+    src = rng.integers(0, V, E)
+    assert E > 4 * 65536
+    ei = torch.from_numpy(np.stack([src, dst]))
+    tc = G.TargetCSR(ei.cuda(), V)
+    perm = tc.perm.cpu().numpy()
+    assert np.array_equal(perm, np.argsort(dst, kind="stable")) and perm.max() >= 4 * 65536
+    assert np.array_equal(tc.col.cpu().numpy(), src[perm])
+    assert np.array_equal(tc.rowptr.cpu().numpy(), np.concatenate([[0], np.cumsum(deg)]))
+    w = torch.from_numpy(rng.random(E).astype(np.float32) + 0.01).cuda()
+    buf = torch.from_numpy(rng.standard_normal(V * H + x_offset).astype(np.float32)).cuda()
+    x = buf[x_offset:].view(V, H)
+    assert x.is_contiguous() and x.data_ptr() % 16 == 4 * x_offset
+    out = G.spmm_csr(tc, x, w[tc.perm].contiguous())
+    s, d = ei[0].cuda(), ei[1].cuda()
+    terms = x.double()[s] * w.double()[:, None]
+    ref = torch.zeros((V, H), dtype=torch.float64, device=x.device).index_add_(0, d, terms)
+    mag = torch.zeros((V, H), dtype=torch.float64, device=x.device).index_add_(0, d, terms.abs())
+    del terms
+    assert bool((out[5] == 0).all())
+    err = (out.double() - ref).abs()
+    assert bool((err <= 2.0 ** -20 * mag + 1e-30).all()), float((err / (mag + 1e-30)).max())
+
+
 def test_graphconv_edge_branch_hip_vs_torch():
     from model.pinsage import PinSage
     torch.manual_seed(3)

@@ -250,3 +250,181 @@ def test_ivf_index_uses_the_inverted_file_and_is_3x_faster_than_flat():
     print(f"IVF (nlist 100, nprobe 20) {t_ivf * 1e3:.3f} ms, flat L2 {t_flat * 1e3:.3f} ms, x{t_flat / t_ivf:.2f}")
     # measured 3.2-3.4 x (profiles/README.md, tools/ivf_probe.py); the assertion leaves room for box-to-box variation
     assert t_flat / t_ivf >= 2.6
+
+
+# ---- query chunking.  ps_dot_topk / ps_l2_topk cut the queries into chunks of chunk_rows(nq, N) = max(64, 2^28 / N) rows (one
+# [chunk, N] similarity slab each); ps_ivf_topk into chunks of ivf_chunk(nq, nprobe, nlist, max_list) queries.  Every later chunk
+# offsets qidx / the query norms / the probe lists / the outputs by its first query q0: the tests below span several chunks,
+# with a ragged last one, and assert that they do.
+
+def _dot_chunk(nq, N, D, k):
+    """chunk rows of ps_dot_topk, read from the library: ps_dot_topk_workspace_bytes = c N 4 + c D 4 + 1024"""
+    from pinsage_hip import native as nv
+    wsb = int(nv.lib().ps_dot_topk_workspace_bytes(nv.i64(nq), nv.i64(N), nv.i32(D), nv.i32(k)))
+    assert (wsb - 1024) % (4 * (N + D)) == 0
+    return (wsb - 1024) // (4 * (N + D))
+
+
+def _l2_chunk(nq, N, D, k):
+    """chunk rows of ps_l2_topk, read from the library: ps_l2_topk_workspace_bytes = c N 4 + (N + nq) 4 + 2048"""
+    from pinsage_hip import native as nv
+    wsb = int(nv.lib().ps_l2_topk_workspace_bytes(nv.i64(nq), nv.i64(N), nv.i32(D), nv.i32(k)))
+    assert (wsb - 2048 - 4 * (N + nq)) % (4 * N) == 0
+    return (wsb - 2048 - 4 * (N + nq)) // (4 * N)
+
+
+def _ivf_chunk(nq, nprobe, nlist, max_list):
+    """dot_topk.hip ivf_chunk(): budget = 2^29 / max_list - 64 nlist queries' worth of slab, divided by nprobe, at least 64"""
+    c = (1 << 29) // max(max_list, 1) - 64 * nlist
+    c = max(c // nprobe, 64)
+    return min(c, nq)
+
+
+def _slices(nq, step):
+    return [(a, min(a + step, nq)) for a in range(0, nq, step)]
+
+
+def _chunk_rows_data(kind, N, D, seed):
+    g = torch.Generator().manual_seed(seed)
+    if kind == "unit":
+        return torch.nn.functional.normalize(torch.randn(N, D, generator=g), dim=1)
+    # tie-heavy: 1 500 distinct rows of {-1, -1/2, 0, 1/2, 1} -- every product and partial sum is exact, so whole runs of
+    # items share a similarity and the id order decides
+    proto = (torch.randint(-2, 3, (1500, D), generator=g).float() * 0.5)
+    return proto[torch.randint(0, 1500, (N,), generator=g)].contiguous()
+
+
+@pytest.mark.parametrize("kind", ["unit", "ties"])
+def test_dot_topk_over_several_chunks_vs_the_slab(kind):
+    """ps_dot_topk at N = 59 047 (chunk_rows = 2^28 / N = 4 546), D = 256, nq = 2 x 4 546 + 7 (three chunks, the last ragged
+    and not a multiple of 4 rows), k in {11, 100} (100 takes several 32-key sweeps), self excluded and not.  Reference: the
+    slab dense.linear(E[q], E) (the same fmaf chain, held to the C oracle by test_linear_vs_oracle), self set to -inf when
+    excluded, then the first k of a stable descending sort (ids ascending among ties): values and ids bit for bit.  The slab
+    itself is held to fp64 within D 2^-24 |a| |b|."""
+    from pinsage_hip import dense
+    N, D = 59047, 256
+    nq = 2 * 4546 + 7
+    E = _chunk_rows_data(kind, N, D, seed=21).cuda()
+    g = torch.Generator().manual_seed(22)
+    qidx = torch.randint(0, N, (nq,), generator=g)
+    qidx[:64] = torch.arange(N - 64, N)                                  # ids far from the query's slot in the batch
+    qidx[-64:] = torch.arange(64)
+    qidx = qidx.cuda()
+    c = _dot_chunk(nq, N, D, 100)
+    assert c == 4546 and nq > 2 * c and (nq - 2 * c) % 4 != 0           # three chunks, the last ragged
+    slab = dense.linear(E[qidx], E)
+    assert not bool(torch.isnan(slab).any())
+    assert not bool(((slab == 0) & torch.signbit(slab)).any())            # no -0.0: the sort's order and the kernel's key order agree
+    E64 = E.double()
+    nrm = E64.norm(dim=1)
+    for r0 in range(0, nq, 1024):                                          # fp64 check of the GEMM itself
+        r1 = min(r0 + 1024, nq)
+        exact = E64[qidx[r0:r1]] @ E64.T
+        bound = D * 2.0 ** -24 * nrm[qidx[r0:r1]][:, None] * nrm[None, :]
+        assert bool(((slab[r0:r1].double() - exact).abs() <= bound).all())
+    del E64
+    rows = torch.arange(nq, device=slab.device)
+    for excl in (True, False):
+        got = {k: dense.dot_topk(E, qidx, k, exclude_self=excl) for k in (11, 100)}
+        for r0 in range(0, nq, 1024):
+            r1 = min(r0 + 1024, nq)
+            s = slab[r0:r1].clone()
+            if excl:
+                s[rows[r0:r1] - r0, qidx[r0:r1]] = float("-inf")
+            sv, si = torch.sort(s, dim=1, descending=True, stable=True)
+            for k, (vals, ids) in got.items():
+                assert torch.equal(ids[r0:r1], si[:, :k]), (excl, k, r0)
+                assert torch.equal(vals[r0:r1].view(torch.int32), sv[:, :k].contiguous().view(torch.int32)), (excl, k, r0)
+        if excl:
+            assert not bool((got[100][1] == qidx[:, None]).any())
+        elif kind == "unit":
+            assert torch.equal(got[11][1][:, 0], qidx)                   # self is nearest
+
+
+def test_chunked_searches_are_batch_invariant():
+    """A query's result does not depend on its neighbours in the batch: one multi-chunk call of dot_topk, l2_topk (plain and
+    masked) equals, under torch.equal, the concatenation of single-chunk calls on slices that do not line up with its chunks."""
+    from pinsage_hip import dense
+    N, D, nlist = 59047, 256, 100
+    nq = 2 * 4546 + 7
+    g = torch.Generator().manual_seed(31)
+    E = torch.nn.functional.normalize(torch.randn(N, D, generator=g), dim=1).cuda()
+    qidx = torch.randint(0, N, (nq,), generator=g).cuda()
+    Q = (E[qidx] + 0.05 * torch.randn(nq, D, generator=g).cuda()).contiguous()
+    assign = torch.randint(0, nlist, (N,), generator=g, dtype=torch.int32)
+    probe_lists = np.stack([np.random.RandomState(r).permutation(nlist)[:20] for r in range(nq)])
+    bits = torch.from_numpy(_probe_bits(probe_lists, nlist).view(np.int32)).cuda()
+    assign = assign.cuda()
+    k, step = 100, 3000
+    assert _dot_chunk(nq, N, D, k) < step * 2 and nq > 2 * _dot_chunk(nq, N, D, k)
+    assert _l2_chunk(nq, N, D, k) < step * 2 and nq > 2 * _l2_chunk(nq, N, D, k)
+    assert all(_dot_chunk(b - a, N, D, k) == b - a for a, b in _slices(nq, step))          # every slice is one chunk
+    v, i = dense.dot_topk(E, qidx, k, exclude_self=True)
+    parts = [dense.dot_topk(E, qidx[a:b], k, exclude_self=True) for a, b in _slices(nq, step)]
+    assert torch.equal(i, torch.cat([p[1] for p in parts])) and torch.equal(v, torch.cat([p[0] for p in parts]))
+    for masked in (False, True):
+        kw = dict(assign=assign, probe=bits) if masked else {}
+        d, i = dense.l2_topk(E, Q, k, **kw)
+        parts = [dense.l2_topk(E, Q[a:b], k, **({} if not masked else dict(assign=assign, probe=bits[a:b].contiguous())))
+                 for a, b in _slices(nq, step)]
+        assert torch.equal(i, torch.cat([p[1] for p in parts])) and torch.equal(d, torch.cat([p[0] for p in parts])), masked
+
+
+def test_inverted_file_scan_over_several_chunks():
+    """ps_ivf_topk with chunks of ivf_chunk(nq, 8, 64, 30 000) = ((2^29 / 30 000 - 64 x 64) / 8) = 1 724 queries (a ~2.2 GB slab
+    per chunk) and nq = 2 x 1 724 + 5: the workspace (bc, cnt, grp, seg, slab) is reused by three chunks, the last ragged.
+    List 0 holds half the items, list 63 none; queries that probe only the empty list, and queries that probe list 0.
+    Against the masked full product (ps_l2_topk) bit for bit, the fp64 "k best (distance, id)" bound, and as one call against
+    single-chunk calls on slices."""
+    from pinsage_hip import dense
+    rs = np.random.RandomState(41)
+    N, D, nlist, nprobe = 60000, 64, 64, 8
+    X = rs.standard_normal((N, D)).astype(np.float32)
+    assign = rs.randint(1, nlist - 1, size=N).astype(np.int32)
+    X[100] = X[7]; X[50000] = X[7]                                          # exact ties (one list): broken by original id
+    assign[[7, 100, 50000]] = 5
+    assign[rs.permutation(np.setdiff1d(np.arange(N), [7, 100, 50000]))[:30000]] = 0     # list 0: 30 000 items; list 63: empty
+    max_list = int(np.bincount(assign, minlength=nlist).max())
+    assert max_list == 30000 and np.bincount(assign, minlength=nlist)[63] == 0
+    c = _ivf_chunk(1 << 20, nprobe, nlist, max_list)
+    assert c == 1724
+    nq = 2 * c + 5
+    assert _ivf_chunk(nq, nprobe, nlist, max_list) == c and nq > 2 * c
+    Q = X[rs.randint(0, N, size=nq)] + 0.3 * rs.standard_normal((nq, D)).astype(np.float32)
+    Q[0] = X[7]
+    probe_lists = np.stack([rs.permutation(nlist)[:nprobe] for _ in range(nq)]).astype(np.int32)
+    probe_lists[::3, 1] = 0                                                 # list 0 in every third query, every chunk
+    probe_lists[0, 0] = 5
+    for r in (1, c - 1, c, 2 * c + 3):
+        probe_lists[r] = 63                                                 # only the empty list: all padding
+    order = np.argsort(assign, kind="stable")
+    list_ptr = np.zeros(nlist + 1, dtype=np.int64)
+    list_ptr[1:] = np.cumsum(np.bincount(assign, minlength=nlist))
+    Xd, Qd = torch.from_numpy(X).cuda(), torch.from_numpy(Q).cuda()
+    Xs, ids_s, lp, pl = Xd[torch.from_numpy(order).cuda()].contiguous(), torch.from_numpy(order), torch.from_numpy(list_ptr), torch.from_numpy(probe_lists)
+    bits = torch.from_numpy(_probe_bits(probe_lists, nlist).view(np.int32)).cuda()
+    vis = torch.from_numpy((probe_lists[:, :, None] == np.arange(nlist)[None, None, :]).any(axis=1)).cuda()[:, torch.from_numpy(assign).long().cuda()]
+    X64, Q64 = Xd.double(), Qd.double()
+    for k in (10, 40):
+        di, ii = dense.ivf_topk(Xs, lp, ids_s, Qd, pl, k)
+        dm, im = dense.l2_topk(Xd, Qd, k, assign=torch.from_numpy(assign).cuda(), probe=bits)
+        assert torch.equal(ii, im) and torch.equal(di, dm), k
+        parts = [dense.ivf_topk(Xs, lp, ids_s, Qd[a:b], pl[a:b], k, max_list=max_list) for a, b in _slices(nq, 1000)]
+        assert torch.equal(ii, torch.cat([p[1] for p in parts])) and torch.equal(di, torch.cat([p[0] for p in parts])), k
+        for r in (1, c - 1, c, 2 * c + 3):
+            assert bool((ii[r] == -1).all()) and bool((di[r] >= 3.0e38).all())
+        assert ii[0, :3].tolist() == [7, 100, 50000]
+        # fp64: the k hits are the k best visible items by (distance, id), up to fp32 near-ties
+        nvis = vis.sum(1)
+        for r0 in range(0, nq, 512):
+            r1 = min(r0 + 512, nq)
+            d2 = (Q64[r0:r1] ** 2).sum(1)[:, None] + (X64 ** 2).sum(1)[None, :] - 2 * Q64[r0:r1] @ X64.T
+            d2 = torch.where(vis[r0:r1], d2, torch.full_like(d2, float("inf")))
+            kk = nvis[r0:r1].clamp(max=k)
+            valid = torch.arange(k, device=kk.device)[None, :] < kk[:, None]
+            hit = ii[r0:r1]
+            assert torch.equal(hit >= 0, valid)                             # k hits, or every visible item and -1 padding
+            kth = torch.sort(d2, dim=1).values.gather(1, (kk - 1).clamp(min=0)[:, None])
+            assert bool((~valid | (d2.gather(1, hit.clamp(min=0)) <= kth + 1e-3)).all())
+            srt = hit.sort(dim=1).values
+            assert not bool(((srt[:, 1:] == srt[:, :-1]) & (srt[:, 1:] >= 0)).any())     # no id twice
