@@ -341,6 +341,45 @@ int ps_ivf_topk(const float *X, int64_t N, int D, const int64_t *list_ptr, int n
 int ps_spmm_csr(const int64_t *rowptr, const int32_t *col, const float *val, const float *x, int64_t N, int H,
                 int64_t V, int64_t E, float *out, ps_stream_t stream);
 
+/* ---- GraphBuilder.build_item_similarity_graph (data/graph_builder.py:59-116): the item co-occurrence graph.
+ * m_ua = number of rating rows (user u, item a); users are RANKS 0..U-1 in the reference's groupby('userId') order.
+ * count(a, b) = sum_u m_ua m_ub (a < b), count(a, a) = sum_u m_ua (m_ua - 1) / 2: an integer GEMM A A^T over K = users,
+ * contracted on the matrix cores from operand planes (csrc/cooc_mfma.hip): fp4 e2m1 when max_mult <= 4, int8 up to 127.
+ *
+ * ps_cooc_planes : the n distinct (user, item) entries with their multiplicity (int32 each, any order) -> planes
+ *                  (ps_cooc_planes_bytes(U, M, max_mult) bytes, 16-byte aligned, zeroed here) and item_stats int64[3 M]:
+ *                  [0, M) sum m (m - 1) / 2, [M, 2M) sum m^2, [2M, 3M) first user with m >= 2 (INT64 0x7f7f.. if none);
+ *                  max_seen int32[1] = the largest multiplicity seen (the caller's max_mult must bound it).
+ *                  max_mult > 127: PS_EUNSUPPORTED.
+ * ps_cooc_pairs  : every pair a <= b < M with count >= thr (thr >= 1) as a record {a, b, count, window}; window = the
+ *                  PS_COOC_WINDOW-user window that holds the first user with m_ua m_ub > 0 (m_ua >= 2 for a == b).  Records
+ *                  are in no particular order.  max_sq = max over items of sum_u m_ua^2 (item_stats[M, 2M)) bounds every
+ *                  count: PS_EUNSUPPORTED if it reaches 2^24 (fp4, f32 accumulation) or 2^31 (int8).  The ONE entry that
+ *                  synchronises its stream: *count (device) and *h_count = the number of surviving pairs; when that exceeds
+ *                  `capacity` the first `capacity` records are written and PS_EWORKSPACE is returned (rerun with more room).
+ * ps_cooc_keys   : per record the reference's dict-insertion key (u, p, q): u = the first common user, p < q the first
+ *                  positions of a and b in u's group (the first two of a when a == b), as
+ *                  keys[k] = (uptr[u] + p) * R + (uptr[u] + q)   (ascending key == the reference's output order).
+ *                  iptr int64[M+1] / iuser int32 / imult int32: the entries grouped by item, users ascending;
+ *                  uptr int64[U+1] / uitem int32[R] / upos int32[R]: the R rows grouped by user, sorted by (item, position);
+ *                  upos = the row's position in its user's group (rows keep their dataframe order there).
+ * ps_cooc_emit   : record perm[k] (perm int64[n], e.g. the argsort of the keys) -> edge_index int64[2, 2n] columns 2k, 2k + 1
+ *                  = [a -> b, b -> a], edge_weight float[2n] = count twice. */
+#define PS_COOC_WINDOW 512
+typedef struct {
+    int32_t a, b, count, window;
+} ps_cooc_record;
+size_t ps_cooc_planes_bytes(int64_t U, int64_t M, int max_mult);
+int ps_cooc_planes(const int32_t *user, const int32_t *item, const int32_t *mult, int64_t n, int64_t U, int64_t M,
+                   int max_mult, void *planes, size_t planes_bytes, int64_t *item_stats, int32_t *max_seen, ps_stream_t stream);
+int ps_cooc_pairs(const void *planes, int64_t U, int64_t M, int max_mult, int64_t max_sq, const int64_t *item_stats, int64_t thr,
+                  ps_cooc_record *records, int64_t capacity, int64_t *count, int64_t *h_count, ps_stream_t stream);
+int ps_cooc_keys(const ps_cooc_record *records, int64_t n, int64_t U, int64_t M, const int64_t *iptr, const int32_t *iuser,
+                 const int32_t *imult, const int64_t *uptr, const int32_t *uitem, const int32_t *upos, int64_t R,
+                 int64_t *keys, ps_stream_t stream);
+int ps_cooc_emit(const ps_cooc_record *records, const int64_t *perm, int64_t n, int64_t *edge_index, float *edge_weight,
+                 ps_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,145 @@
+"""Item co-occurrence graph of GraphBuilder.build_item_similarity_graph (reference data/graph_builder.py:59-116) on the device.
+
+The reference walks every user's group (groupby('userId'): ascending raw user id, rows in dataframe order) and bumps a dict
+entry for every ordered pair of positions; a pair with count >= threshold becomes the two edges [a -> b, b -> a] (a <= b) in
+dict insertion order.  Here the counts are one integer GEMM A A^T over the (user, item) multiplicities on the matrix cores
+(csrc/cooc_mfma.hip), and the insertion order is rebuilt exactly: a pair enters the dict at (u, p, q) = its first user in
+groupby order and the first positions of its items in that user's group (the first two of the item for a self pair), so
+sorting the surviving pairs by that key reproduces the reference's edge list, order included.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import torch
+
+from . import native as nv
+
+WINDOW = 512                         # PS_COOC_WINDOW (include/pinsage_hip.h)
+_RECORD_BYTES = 16
+_FIRST_CAPACITY = 1 << 28            # records (4 GiB) tried first; a larger result reruns the pass once at its exact size
+
+
+def effective_threshold(threshold):
+    """The integer t with (count >= threshold) == (count >= t) for every count >= 1 (a pair with count 0 never enters the
+    reference's dict); None when no count can pass."""
+    t = float(threshold)
+    if math.isnan(t) or t > 2.0 ** 62:
+        return None
+    return 1 if t < 1 else math.ceil(t)
+
+
+class _Prep:
+    """Rows ranked and sorted on the device: user ranks in groupby order, rows grouped by user, distinct entries."""
+
+    def __init__(self, user_ids, item_idx, num_items, dev):
+        uid = torch.as_tensor(user_ids).to(dev, torch.int64).reshape(-1)
+        it = torch.as_tensor(item_idx).to(dev, torch.int64).reshape(-1)
+        if uid.numel() != it.numel():
+            raise ValueError("user_ids and item_idx must have the same length")
+        M = int(num_items)
+        R = it.numel()
+        if M <= 0:
+            raise ValueError("num_items must be positive")
+        if R >= 2 ** 31 - 1:
+            raise ValueError("more than 2^31 - 2 rating rows")
+        if R and (int(it.min()) < 0 or int(it.max()) >= M):
+            raise ValueError("item index out of range [0, num_items)")
+        self.M, self.R = M, R
+        _, urank = torch.unique(uid, sorted=True, return_inverse=True)       # groupby('userId') order
+        self.U = U = int(urank.max()) + 1 if R else 1
+        order_u = torch.sort(urank, stable=True).indices                     # (user, row)
+        cnt = torch.bincount(urank, minlength=U)
+        self.uptr = torch.zeros(U + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(cnt, 0, out=self.uptr[1:])
+        ur = urank[order_u]
+        pos = torch.arange(R, device=dev) - self.uptr[ur]
+        k1 = ur * M + it[order_u]
+        s1 = torch.sort(k1, stable=True)                                     # (user, item, position)
+        self.uitem = (s1.values % M).to(torch.int32)
+        self.upos = pos[s1.indices].to(torch.int32)
+        ekey, mult = torch.unique_consecutive(s1.values, return_counts=True)
+        eu, ei = ekey // M, ekey % M
+        s2 = torch.sort(ei * U + eu).indices                                 # distinct entries by (item, user)
+        self.iuser = eu[s2].to(torch.int32)
+        self.iitem = ei[s2].to(torch.int32)
+        self.imult = mult[s2].to(torch.int32)
+        self.iptr = torch.zeros(M + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(torch.bincount(ei, minlength=M), 0, out=self.iptr[1:])
+        self.max_mult = int(mult.max()) if R else 1
+        # ordered position pairs (the reference's dict updates): bounds the number of surviving pairs
+        d = cnt.to(torch.float64)
+        self.updates = int((d * (d - 1) / 2).sum())
+
+
+def item_cooccurrence_graph(user_ids, item_idx, num_items, threshold=5, device="cuda", capacity=None, timer=None):
+    """-> (edge_index int64[2, 2P], edge_weight fp32[2P]) on `device`: the reference's item similarity graph for the rating
+    rows (user_ids[r], item_idx[r]) in dataframe order.  user_ids are the raw ids (grouped in ascending order), item_idx the
+    mapped item indices in [0, num_items).  `capacity` (records) overrides the first size of the pair buffer; a buffer that
+    turns out too small is reallocated once at the exact size and the pass rerun.  A multiplicity above 127 raises
+    ValueError.  `timer`, if given, is a callable(name) invoked after each phase (for tools/cooc_probe.py)."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise nv.NativeError("item_cooccurrence_graph runs on the MI355X; there is no CPU fallback")
+    tick = timer or (lambda name: None)
+    P = _Prep(user_ids, item_idx, num_items, dev)
+    tick("prep")
+    thr = effective_threshold(threshold)
+    if P.R == 0 or thr is None:
+        return torch.empty((2, 0), dtype=torch.int64, device=dev), torch.empty((0,), dtype=torch.float32, device=dev)
+    if P.max_mult > 127:
+        raise ValueError(f"a (user, item) pair occurs {P.max_mult} times; the co-occurrence GEMM takes multiplicities up to 127")
+    U, M, R = P.U, P.M, P.R
+    lib = nv.lib()
+    nbytes = lib.ps_cooc_planes_bytes(nv.i64(U), nv.i64(M), nv.i32(P.max_mult))
+    if nbytes == 0:
+        raise ValueError(f"co-occurrence shape not supported (users {U}, items {M})")
+    planes = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    stats = torch.empty(3 * M, dtype=torch.int64, device=dev)
+    seen = torch.empty(1, dtype=torch.int32, device=dev)
+    st = nv.stream()
+    nv.call("ps_cooc_planes", nv.ptr(P.iuser), nv.ptr(P.iitem), nv.ptr(P.imult), nv.i64(P.iuser.numel()), nv.i64(U), nv.i64(M),
+            nv.i32(P.max_mult), nv.ptr(planes), C.c_size_t(nbytes), nv.ptr(stats), nv.ptr(seen), st)
+    max_sq = int(stats[M:2 * M].max())
+    if int(seen) != P.max_mult:
+        raise nv.NativeError(f"ps_cooc_planes saw multiplicity {int(seen)}, expected {P.max_mult}")
+    tick("planes")
+    if capacity is None:
+        # no pair count is known before the contraction: room for every possible pair, up to _FIRST_CAPACITY records and a
+        # quarter of the free memory
+        cap = min(P.updates + M, M * (M + 1) // 2, _FIRST_CAPACITY, torch.cuda.mem_get_info(dev)[0] // (4 * _RECORD_BYTES))
+    else:
+        cap = int(capacity)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    h_count = C.c_int64(0)
+    for attempt in range(2):
+        rec = torch.empty((max(cap, 1), 4), dtype=torch.int32, device=dev)
+        rc = lib.ps_cooc_pairs(nv.ptr(planes), nv.i64(U), nv.i64(M), nv.i32(P.max_mult), nv.i64(max_sq), nv.ptr(stats), nv.i64(thr),
+                               nv.ptr(rec), nv.i64(cap), nv.ptr(count), C.byref(h_count), st)
+        if rc == nv.PS_EWORKSPACE and attempt == 0:
+            cap = int(h_count.value)
+            del rec
+            continue
+        if rc == nv.PS_EUNSUPPORTED:
+            raise ValueError(f"co-occurrence counts may reach {max_sq}: beyond the exact range of the "
+                             f"{'fp4' if P.max_mult <= 4 else 'int8'} contraction")
+        nv.check(rc, "ps_cooc_pairs")
+        break
+    n = int(h_count.value)
+    del planes
+    rec = rec[:n].clone() if rec.size(0) > n else rec             # frees the first buffer before keys / sort / emit
+    tick("pairs")
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    nv.call("ps_cooc_keys", nv.ptr(rec), nv.i64(n), nv.i64(U), nv.i64(M), nv.ptr(P.iptr), nv.ptr(P.iuser), nv.ptr(P.imult),
+            nv.ptr(P.uptr), nv.ptr(P.uitem), nv.ptr(P.upos), nv.i64(R), nv.ptr(keys), st)
+    tick("keys")
+    if n and int(keys.min()) < 0:
+        raise nv.NativeError("ps_cooc_keys found no first common user for some pair")
+    perm = torch.sort(keys).indices
+    del keys
+    edge_index = torch.empty((2, 2 * n), dtype=torch.int64, device=dev)
+    edge_weight = torch.empty(2 * n, dtype=torch.float32, device=dev)
+    nv.call("ps_cooc_emit", nv.ptr(rec), nv.ptr(perm), nv.i64(n), nv.ptr(edge_index), nv.ptr(edge_weight), st)
+    tick("order")
+    return edge_index, edge_weight
