@@ -380,6 +380,39 @@ int ps_cooc_keys(const ps_cooc_record *records, int64_t n, int64_t U, int64_t M,
 int ps_cooc_emit(const ps_cooc_record *records, const int64_t *perm, int64_t n, int64_t *edge_index, float *edge_weight,
                  ps_stream_t stream);
 
+/* ---- the ranking losses of model/loss.py (MaxMarginRankingLoss :6-64, BatchHardTripletLoss :66-113, CurriculumLoss :115-177):
+ * loss = mean_b relu((margin + max_j Q_b . X_j) - Q_b . P_b), from one (maximum, arg-max) pair per query row.
+ *
+ * ps_hardest_negative : best[b] = the largest similarity Q_b . X_j and the SMALLEST j that attains it, packed in one word
+ *                       (best uint64[B], 8-byte aligned, overwritten); sim float[B] / idx int64[B] (either may be NULL) receive
+ *                       the pair unpacked.  flags 0: shared candidates X float[N, D] -- ps_linear's fp32-MFMA tiles with a
+ *                       row-arg-max epilogue, sim[b] is bit-identical to ps_linear(Q, X)[b, idx[b]], no [B, N] slab is written;
+ *                       PS_HN_EXCLUDE_DIAG: candidate j == b is left out (batch-hard: X = the positives; a row left without a
+ *                       candidate gets -inf / -1).  PS_HN_PER_QUERY: X float[B, N, D], row b sees X[b] only -- the fmaf chain
+ *                       of ps_row_dot, bit-identical to the shared form on equal data.  A NaN similarity is its row's maximum.
+ *                       N == 0 with B > 0: PS_EINVAL.  B, N < 2^31.
+ * ps_margin_loss      : with pos_b = ps_row_dot's Q_b . P_b: row_loss[b] = relu((margin + sim_b) - pos_b) (float[B], workspace),
+ *                       active uint8[B] = the rows relu passes a gradient through, idx int64[B] = the arg-max, loss float[1] =
+ *                       sum(row_loss) / B by a reduction of fixed shape (the same bits on every run).
+ * ps_margin_loss_bwd  : g_b = grad_out[0] / B on active rows, 0 elsewhere (grad_out: DEVICE float[1]); a_b = idx[b].
+ *                       dQ[b] = g_b X[a_b] + (-g_b P[b]);  dP[b] = -g_b Q[b];
+ *                       PS_LOSS_PER_QUERY (X [B, N, D]): dX[b, a_b] = g_b Q[b], +0.0 elsewhere;
+ *                       PS_LOSS_SHARED (X [N, D]): dX[j] = sum over {b : a_b = j, active} of g_b Q[b], b ascending;
+ *                       PS_LOSS_BATCH_HARD (X = NULL, N = B, dX = NULL): X = P above and dP[j] = (-g_j Q[j]) + that sum.
+ *                       Every product and sum is one rounded fp32 operation in the order written; sums over rows are taken in
+ *                       ascending row order by one wave (no float atomics): deterministic.  dQ / dP / dX: NULL = not computed. */
+#define PS_HN_PER_QUERY 1
+#define PS_HN_EXCLUDE_DIAG 2
+#define PS_LOSS_SHARED 0
+#define PS_LOSS_PER_QUERY 1
+#define PS_LOSS_BATCH_HARD 2
+int ps_hardest_negative(const float *Q, int64_t B, int D, const float *X, int64_t N, int flags, uint64_t *best, float *sim,
+                        int64_t *idx, ps_stream_t stream);
+int ps_margin_loss(const float *Q, const float *P, int64_t B, int D, const uint64_t *best, float margin, float *row_loss,
+                   int64_t *idx, uint8_t *active, float *loss, ps_stream_t stream);
+int ps_margin_loss_bwd(const float *Q, const float *P, const float *X, int64_t B, int64_t N, int D, int mode, const int64_t *idx,
+                       const uint8_t *active, const float *grad_out, float *dQ, float *dP, float *dX, ps_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,8 @@ struct GemmArgs {
     int64_t max_idx;
     // EPI 2 (ps_rank_count): per row the target's similarity and id, the id of column 0, the counts (+=)
     const float *thr; const int64_t *tgt; int64_t id_off; int64_t *cnt;
+    // EPI 3 (ps_hardest_negative): per row the largest ps_best_pack(similarity, column) (max=); xdiag: column == row is no candidate
+    unsigned long long *best; int xdiag;
 };
 
 // 8 consecutive k of one row (zero-filled outside [0,K) / invalid row)
@@ -236,6 +238,39 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, f32x16 (&acc)[T
 #pragma unroll
             for (int w = 0; w < WN; ++w) t += sCnt[tid * WN + w];
             if (m0 + tid < g.M && t != 0) atomicAdd(reinterpret_cast<unsigned long long *>(g.cnt + m0 + tid), (unsigned long long)t);
+        }
+        PS_TRACE(41);
+        return;
+    }
+    if constexpr (EPI == 3) {
+        // ps_hardest_negative: per row the largest similarity and the smallest column that attains it, as one packed word
+        // (ps_best_pack, csrc/ps_common.h).  A lane folds its TN columns of a row, the 32 lanes of a wave half take the integer
+        // maximum, lane r of each half keeps row r's word and adds it to the row's total with ONE vector 64-bit atomic max per
+        // 32-row tile (16 rows per half).  Integer max is associative: any order of the column tiles gives the same word.  No
+        // [M, N] slab is written.
+#pragma unroll
+        for (int a = 0; a < TM; ++a) {
+            unsigned long long mine = 0ull;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int64_t row = m0 + (wm * TM + a) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                unsigned long long w = 0ull;
+#pragma unroll
+                for (int b = 0; b < TN; ++b) {
+                    const int col = n0 + (wn * TN + b) * 32 + li;
+                    const unsigned long long c = ps_best_pack(acc[a][b][r], (uint32_t)col);
+                    const bool ok = col < g.N && !(g.xdiag && (int64_t)col == row);
+                    w = ok && c > w ? c : w;
+                }
+#pragma unroll
+                for (int off = 1; off < 32; off <<= 1) {
+                    const unsigned long long o = __shfl_xor(w, off);
+                    w = o > w ? o : w;
+                }
+                if (li == r) mine = w;
+            }
+            const int64_t row = m0 + (wm * TM + a) * 32 + (li & 3) + 8 * ((li & 15) >> 2) + 4 * lh;
+            if (li < 16 && row < g.M && mine != 0ull) atomicMax(g.best + row, mine);
         }
         PS_TRACE(41);
         return;
@@ -1538,18 +1573,29 @@ __global__ void row_dot_kernel(const float *__restrict__ A, int64_t nA, const fl
 
 // the tiles of a plain ps_linear of the same shape (launch_gemm_v without the fused norm): persistent 64 x 128 tiles for aligned
 // operands, the one-tile kernel otherwise
-template <bool FAST>
+template <int EPI, bool FAST>
 int launch_rank(const GemmArgs &g, hipStream_t st) {
-    if (FAST && g.N > 128) return launch_persistent<2, 2, 1, 2, 2>(g, st);
+    if (FAST && g.N > 128) return launch_persistent<2, 2, 1, 2, EPI>(g, st);
     const int64_t tiles_n = ps_cdiv(g.N, 128);
     if (tiles_n > 65535) return PS_EUNSUPPORTED;
     dim3 grid((unsigned)ps_cdiv(g.M, 64), (unsigned)tiles_n);
-    hipLaunchKernelGGL((gemm_f32_kernel<2, 2, 1, 2, 32, 2, FAST>), grid, dim3(256), 0, st, g);
+    hipLaunchKernelGGL((gemm_f32_kernel<2, 2, 1, 2, 32, EPI, FAST>), grid, dim3(256), 0, st, g);
     PS_CHECK_LAUNCH();
     return PS_OK;
 }
 
 }  // namespace
+
+// ps_hardest_negative's shared-candidate product: the tiles of ps_rank_count with the EPI 3 epilogue
+int psi_hardest_shared(const float *Q, int64_t B, int D, const float *X, int64_t N, int exclude_diag, unsigned long long *best,
+                       ps_stream_t stream) {
+    if (B <= 0 || N <= 0 || N > 0x7fffffff || D <= 0 || !Q || !X || !best || reinterpret_cast<size_t>(best) % 8 != 0) return PS_EINVAL;
+    GemmArgs g{Q, B, D, X, D, nullptr, 0, nullptr, 0, nullptr, (int)N, 0, nullptr, nullptr, 0};
+    g.best = best;
+    g.xdiag = exclude_diag;
+    hipStream_t st = ps_stream(stream);
+    return aligned_operand(Q, D, D) && aligned_operand(X, D, D) ? launch_rank<3, true>(g, st) : launch_rank<3, false>(g, st);
+}
 
 extern "C" int ps_row_dot(const float *A, int64_t nA, const float *B, int64_t nB, int D, const int64_t *ia, const int64_t *ib,
                           int64_t n, float *out, ps_stream_t stream) {
@@ -1575,5 +1621,5 @@ extern "C" int ps_rank_count(const float *E, int64_t N, int D, int64_t id_offset
     g.id_off = id_offset;
     g.cnt = count;
     hipStream_t st = ps_stream(stream);
-    return aligned_operand(Q, D, D) && aligned_operand(E, D, D) ? launch_rank<true>(g, st) : launch_rank<false>(g, st);
+    return aligned_operand(Q, D, D) && aligned_operand(E, D, D) ? launch_rank<2, true>(g, st) : launch_rank<2, false>(g, st);
 }

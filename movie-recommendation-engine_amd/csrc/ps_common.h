@@ -31,7 +31,30 @@ static inline int64_t ps_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 int psi_linear_grouped(const float *x, int64_t M, int K, const float *W, int ldw, float *y, const int64_t *grp, int max_cols,
                        ps_stream_t stream);
 
+// internal: the shared-candidate product of ps_hardest_negative (csrc/loss.hip), ps_linear's tiles with a row-arg-max epilogue
+// (csrc/dense_mfma.hip, EPI 3).  best[b] (zeroed by the caller) = max over the candidates of ps_best_pack(Q_b . X_j, j).
+int psi_hardest_shared(const float *Q, int64_t B, int D, const float *X, int64_t N, int exclude_diag, unsigned long long *best,
+                       ps_stream_t stream);
+
 __device__ __forceinline__ int ps_lane() { return threadIdx.x & 63; }
+
+// (similarity, candidate index) as ONE unsigned word whose integer order is "larger similarity first, then smaller index":
+// high half = the float's place in its total order (-inf < ... < -0 < +0 < ... < +inf, every NaN above +inf: a NaN candidate
+// is its row's maximum, as in torch.max), low half = ~index.  Every word of a real candidate is > 0, so 0 = "no candidate",
+// and partial maxima combine with a 64-bit integer max -- in registers or with a vector atomic -- in any order.
+__device__ __forceinline__ unsigned long long ps_best_pack(float v, uint32_t j) {
+    const int32_t b = __float_as_int(v);
+    const uint32_t key = v != v ? 0xffffffffu : (uint32_t)(b ^ ((b >> 31) & 0x7fffffff)) ^ 0x80000000u;
+    return ((unsigned long long)key << 32) | (uint32_t)~j;
+}
+__device__ __forceinline__ float ps_best_sim(unsigned long long w) {       // 0 (no candidate) -> -inf
+    const uint32_t key = (uint32_t)(w >> 32);
+    if (w == 0ull) return __int_as_float((int)0xff800000u);
+    if (key == 0xffffffffu) return __int_as_float(0x7fc00000);
+    const int32_t k = (int32_t)(key ^ 0x80000000u);
+    return __int_as_float(k ^ ((k >> 31) & 0x7fffffff));
+}
+__device__ __forceinline__ int64_t ps_best_idx(unsigned long long w) { return w == 0ull ? -1 : (int64_t)(uint32_t)~(uint32_t)w; }
 
 // All LDS traffic of a wave is issued in order; this makes earlier LDS writes/atomics of the
 // wave visible to all of its lanes (waits lgkmcnt) and stops the compiler reordering across it.

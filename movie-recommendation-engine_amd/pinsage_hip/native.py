@@ -20,6 +20,8 @@ PS_WALK_HALF_BUCKETS = 0x100
 PS_RELU = 1
 PS_L2NORM = 2
 PS_WPERM = 4
+PS_HN_PER_QUERY, PS_HN_EXCLUDE_DIAG = 1, 2
+PS_LOSS_SHARED, PS_LOSS_PER_QUERY, PS_LOSS_BATCH_HARD = 0, 1, 2
 PS_OK, PS_EINVAL, PS_ELAUNCH, PS_EWORKSPACE, PS_EUNSUPPORTED = 0, -1, -2, -3, -4      # status codes (include/pinsage_hip.h)
 
 
@@ -39,6 +41,7 @@ SYMBOLS = [
     "ps_lsh_planes_bytes", "ps_lsh_expand", "ps_hamming_topk_mfma_workspace_bytes", "ps_hamming_topk_mfma", "ps_hamming_topk_mfma_codes",
     "ps_topk_merge", "ps_topk_merge_strided", "ps_dot_topk_workspace_bytes", "ps_dot_topk", "ps_row_dot", "ps_rank_count", "ps_l2_topk_workspace_bytes", "ps_l2_topk", "ps_ivf_topk_workspace_bytes", "ps_ivf_topk", "ps_spmm_csr",
     "ps_cooc_planes_bytes", "ps_cooc_planes", "ps_cooc_pairs", "ps_cooc_keys", "ps_cooc_emit",
+    "ps_hardest_negative", "ps_margin_loss", "ps_margin_loss_bwd",
 ]
 
 
