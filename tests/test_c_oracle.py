@@ -123,3 +123,34 @@ def test_hamming_and_dot_topk():
     for r, qi in enumerate(q):
         _, ref = orc.exact_topk(E, int(qi), 11)
         assert np.array_equal(i[r], ref)
+
+
+@pytest.mark.parametrize("cs,N,nq,k,kind", [
+    (128, 1000, 7, 64, "random"), (128, 700, 5, 64, "few"), (128, 300, 5, 64, "same"),      # 1024-bit codes, a full wave of k
+    (128, 40, 5, 64, "random"), (32, 5, 3, 40, "few"), (4, 1, 4, 5, "same"), (4, 63, 5, 64, "random"),   # N < k: padding
+    (128, 0, 3, 64, "random"), (4, 0, 1, 1, "same"),                                        # empty table: padding only
+    (4, 3000, 9, 33, "few"), (64, 257, 5, 17, "same"), (16, 700, 9, 63, "few"),
+])
+def test_hamming_references_agree(cs, N, nq, k, kind):
+    """The two references that tests/test_hip_hamming_popcount.py holds the popcount kernel to -- this C oracle and the numpy
+    restatement written there (unpackbits of the XOR, lexsort by (distance, id)) -- agree bit for bit where the GPU tests
+    rely on them alone: 1024-bit codes with k = 64, N < k and N = 0 (the oracle accepts an empty table and pads every
+    position itself), one repeated code and a handful of distinct codes, with and without an id offset."""
+    from test_hip_hamming_popcount import INT_MAX, cut_and_offset, make_case, np_hamming_topk, oracle_hamming_topk, plant_positions
+    q, codes, pos = make_case(cs, N, nq, kind, seed=cs + N + k)
+    assert pos == plant_positions(N) and codes.shape == (N, cs) and q.shape == (nq, cs)
+    ref = np_hamming_topk(q, codes, 64)
+    kk = min(k, N)
+    for off in (0, 2 ** 33 + 5):
+        dn, idn = cut_and_offset(ref, k, off)
+        do, ido = oracle_hamming_topk(q, codes, k, off)
+        assert dn.dtype == do.dtype == np.int32 and idn.dtype == ido.dtype == np.int64
+        assert np.array_equal(dn, do) and np.array_equal(idn, ido)
+        assert np.all(do[:, kk:] == INT_MAX) and np.all(ido[:, kk:] == -1)
+        assert np.all(ido[:, :kk] >= off) and np.all(ido < N + off)
+        # the oracle's own padding and offset, untouched by the wrapper
+        rd, ri = co.hamming_topk(q, codes, k, id_offset=off, threads=3)
+        assert np.array_equal(ri, ido) and np.all(rd[:, kk:] == np.float32(2147483647.0))
+        assert np.array_equal(rd[:, :kk].astype(np.int32), do[:, :kk])
+    lead = (list(range(N)) if kind == "same" else pos)[:k]
+    assert ref[1][0, :len(lead)].tolist() == lead and not ref[0][0, :len(lead)].any()
