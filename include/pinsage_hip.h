@@ -203,7 +203,14 @@ int ps_mt19937_random_sample(const uint32_t *state_in, int pos_in, int64_t skip,
  * Row i: keep j < nvalid[i] with 0 <= ids[i,j] <= max_idx (:123-129); w_j = fp32(count_j/total);
  * w /= sum(w) if > 0 (:140-143); out = sum_j w_j * x[ids_j] (:146); zeros if none (:115-117,:132-134).
  * If wts != NULL (float[B,T]) it supplies w_j directly instead of counts (list API with arbitrary
- * weights; aggregators).  renorm = 0 skips the `w /= sum(w)` step (weights already final). */
+ * weights; aggregators).  renorm = 0 skips the `w /= sum(w)` step (weights already final).
+ * nvalid[i] above T means T (nothing is read beyond row i's T entries) and a negative nvalid[i] means 0, here and in
+ * ps_gcn_layer.  max_idx above N - 1 means N - 1.  `total` is the int32 sum of counts[i, j < nvalid[i]], dropped ids included.
+ * Arithmetic (oracle/pinsage_oracle.c: orc_importance_pool_ex restates it bit for bit): dropped entries carry weight +0; the
+ * fp32 sum of the weights is a pairwise tree over the lanes that hold them (entry e in lane e % 16 of a 16-lane group for
+ * T <= 64 with H % 4 == 0 and 16-byte aligned x / out; in lane e % 64 of the wave otherwise), the division by it an IEEE fp32
+ * division, and out[i, c] the chain acc = fmaf(x[ids_j, c], w_j, acc) over j = 0 .. nvalid[i] - 1 from +0.  For T <= 16 both
+ * lane layouts give the same bits. */
 int ps_importance_pool(const float *x, int64_t N, int H, const int32_t *ids, const int32_t *counts,
                        const float *wts, const int32_t *nvalid, int64_t B, int T, int64_t max_idx,
                        int renorm, float *out, ps_stream_t stream);

@@ -35,7 +35,8 @@ __global__ __launch_bounds__(256) void importance_pool_kernel(const float *__res
             if (counts) cnt0 = counts[i * T + lane];
             if (wts) wt0 = wts[i * T + lane];
         }
-        const int k = __builtin_amdgcn_readfirstlane(nvalid[i]);
+        int k = __builtin_amdgcn_readfirstlane(nvalid[i]);
+        k = k < T ? k : T;                                // nvalid[i] above T means T (as pool4_row): nothing is read beyond row i
         // ---- weights: total of the kept counts (reference: weights = count / sum(top counts)) ----
         int tot = 0;
         if (small) {

@@ -140,6 +140,31 @@ def importance_pool(x, ids, counts, nvalid, threads=1):
     return out
 
 
+def pool_ex(x, ids, counts=None, wts=None, nvalid=None, max_idx=None, renorm=True, lanes=16, threads=1):
+    """orc_importance_pool_ex: ps_importance_pool / ps_gcn_layer's pooling bit for bit (int32 ids, counts or fp32 wts, nvalid
+    clamped to T, ids kept in 0 .. min(max_idx, N - 1)).  lanes = 16: the weight sum in the order of the four-rows-per-wave
+    kernel and the fused layer; lanes = 64: in the order of the one-wave-per-row kernel (orc_importance_pool_lanes)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    counts = None if counts is None else np.ascontiguousarray(counts, dtype=np.int32)
+    wts = None if wts is None else np.ascontiguousarray(wts, dtype=np.float32)
+    nvalid = np.ascontiguousarray(nvalid, dtype=np.int32)
+    B, T = ids.shape
+    N, H = x.shape
+    if nvalid.shape != (B,) or (counts is not None and counts.shape != (B, T)) or (wts is not None and wts.shape != (B, T)):
+        raise ValueError("shape mismatch")
+    if max_idx is None:
+        max_idx = N - 1
+    out = np.empty((B, H), dtype=np.float32)
+    args = (_p(x), C.c_int64(N), C.c_int(H), _p(ids), _p(counts), _p(wts), _p(nvalid), C.c_int64(B), C.c_int(T),
+            C.c_int64(int(max_idx)), C.c_int(int(renorm)))
+    if lanes == 16:
+        _check(lib().orc_importance_pool_ex(*args, _p(out), C.c_int(threads)), "orc_importance_pool_ex")
+    else:
+        _check(lib().orc_importance_pool_lanes(*args, C.c_int(int(lanes)), _p(out), C.c_int(threads)), "orc_importance_pool_lanes")
+    return out
+
+
 def linear(x, W, b=None, x2=None, W2=None, relu=False, l2norm=False, threads=1):
     x = np.ascontiguousarray(x, dtype=np.float32)
     W = np.ascontiguousarray(W, dtype=np.float32)

@@ -274,6 +274,83 @@ int orc_importance_pool(const float *x, int64_t N, int H, const int64_t *ids, co
     return ORC_OK;
 }
 
+/* ---------- a5, bit for bit: the arithmetic of ps_importance_pool / ps_gcn_layer (csrc/pool_row.h, csrc/importance_pool.hip,
+ * include/pinsage_hip.h), serial and in plain C.  Per row i:
+ *   k     = min(nvalid[i], T), a negative value counts as 0;
+ *   tot   = int32 sum of counts[i, :k], dropped entries included (wrapping, as the device adds);
+ *   w_j   = wts[i, j], or (float)((double)count_j / (double)tot);
+ *   kept  iff j < k && 0 <= id <= min(max_idx, N - 1); a dropped entry has weight +0;
+ *   wsum  = the fp32 pairwise tree of the kernels' DPP butterfly over `lanes` lanes (16: the four-rows-per-wave kernel and the
+ *           fused layer; 64: the one-wave-per-row kernel): entry e sits in lane e % lanes of page e / lanes, each lane sums its
+ *           pages in page order from +0, every group of 16 lanes is combined as ((a0+a1)+(a2+a3)) + ((a4+a5)+(a6+a7)), the same
+ *           for lanes 8..15, then the two halves; with 64 lanes the four groups R0..R3 then as (R3 + R2) + (R1 + R0)
+ *           (row_bcast:15 into rows 1 and 3, row_bcast:31 into row 3, lane 63 read).  The kernels hold 1 page for T <= 16 and 4
+ *           for T <= 64 at 16 lanes; an empty page adds +0, so ceil(T / lanes) pages give the same bits;
+ *   if renorm && wsum > 0: every kept weight becomes w / wsum (fp32 division);
+ *   out[i, c] = the chain acc = fmaf(x[id_j, c], w_j, acc) over j = 0 .. k - 1 in order from +0; a dropped entry contributes
+ *           fmaf(+0, +0, acc).  (The kernels walk a few more dropped entries, up to their batch size: the same bits unless acc
+ *           is -0, which a chain from +0 reaches only by underflow.)
+ * Explicit fmaf: the Makefile turns contraction off. */
+static float orc_tree16(const float *a) {
+    return (((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]))) +
+           (((a[8] + a[9]) + (a[10] + a[11])) + ((a[12] + a[13]) + (a[14] + a[15])));
+}
+
+int orc_importance_pool_lanes(const float *x, int64_t N, int H, const int32_t *ids, const int32_t *counts /*nullable*/,
+                              const float *wts /*nullable*/, const int32_t *nvalid, int64_t B, int T, int64_t max_idx,
+                              int renorm, int lanes, float *out, int threads) {
+    if (B < 0 || H <= 0 || T <= 0 || N < 0 || (lanes != 16 && lanes != 64)) return ORC_EINVAL;
+    if (B == 0) return ORC_OK;
+    if (!x || !ids || !nvalid || !out || (!counts && !wts)) return ORC_EINVAL;
+    if (max_idx > N - 1) max_idx = N - 1;
+    int rc = ORC_OK;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static) num_threads(threads > 0 ? threads : 1)
+#endif
+    for (int64_t i = 0; i < B; i++) {
+        float *w = (float *)malloc(sizeof(float) * (size_t)T);
+        if (!w) { rc = ORC_ENOMEM; continue; }
+        const int32_t *id = ids + i * T;
+        int k = nvalid[i];
+        k = k < 0 ? 0 : (k < T ? k : T);
+        uint32_t utot = 0;
+        if (counts) for (int j = 0; j < k; j++) utot += (uint32_t)counts[i * T + j];
+        const int32_t tot = (int32_t)utot;
+        float lane_sum[64];
+        for (int l = 0; l < 64; l++) lane_sum[l] = 0.f;
+        for (int j = 0; j < T; j++) {                                   /* pages in page order: j ascends within a lane */
+            const int keep = j < k && id[j] >= 0 && (int64_t)id[j] <= max_idx;
+            w[j] = keep ? (wts ? wts[i * T + j] : (float)((double)counts[i * T + j] / (double)tot)) : 0.f;
+            lane_sum[j % lanes] += w[j];
+        }
+        float wsum = orc_tree16(lane_sum);
+        if (lanes == 64) {
+            const float r1 = orc_tree16(lane_sum + 16), r2 = orc_tree16(lane_sum + 32), r3 = orc_tree16(lane_sum + 48);
+            wsum = (r3 + r2) + (r1 + wsum);
+        }
+        if (renorm && wsum > 0.f)
+            for (int j = 0; j < k; j++)
+                if (id[j] >= 0 && (int64_t)id[j] <= max_idx) w[j] = w[j] / wsum;
+        float *o = out + i * H;
+        for (int c = 0; c < H; c++) {
+            float acc = 0.f;
+            for (int j = 0; j < k; j++) {
+                const int keep = id[j] >= 0 && (int64_t)id[j] <= max_idx;
+                acc = fmaf(keep ? x[(int64_t)id[j] * H + c] : 0.f, w[j], acc);
+            }
+            o[c] = acc;
+        }
+        free(w);
+    }
+    return rc;
+}
+
+int orc_importance_pool_ex(const float *x, int64_t N, int H, const int32_t *ids, const int32_t *counts /*nullable*/,
+                           const float *wts /*nullable*/, const int32_t *nvalid, int64_t B, int T, int64_t max_idx, int renorm,
+                           float *out, int threads) {
+    return orc_importance_pool_lanes(x, N, H, ids, counts, wts, nvalid, B, T, max_idx, renorm, 16, out, threads);
+}
+
 /* ---------- dense: y = act(x W^T + b), optional row L2 normalise (F.normalize eps 1e-12) --
  * k-ordered fp32 fma chain from 0, bias added last (what the MFMA kernel computes).  */
 int orc_linear(const float *x, const float *W, const float *b, int64_t M, int K, int N,
