@@ -364,6 +364,21 @@ int ps_spmm_csr(const int64_t *rowptr, const int32_t *col, const float *val, con
  *                  count: PS_EUNSUPPORTED if it reaches 2^24 (fp4, f32 accumulation) or 2^31 (int8).  The ONE entry that
  *                  synchronises its stream: *count (device) and *h_count = the number of surviving pairs; when that exceeds
  *                  `capacity` the first `capacity` records are written and PS_EWORKSPACE is returned (rerun with more room).
+ * ps_cooc_pairs_sparse : the same records as ps_cooc_pairs from the entry lists instead of planes (csrc/cooc_sparse.hip): a
+ *                  row-wise sparse A A^T over the upper triangle with an LDS accumulator per item row.  No multiplicity limit,
+ *                  no U x M storage, work = the reference's own pair updates.  The n distinct entries grouped by item
+ *                  (iptr int64[M+1] / iuser / imult int32[n], users ascending inside an item: the arrays ps_cooc_keys takes)
+ *                  and by user (eptr int64[U+1] / eitem / emult int32[n], items ascending inside a user); order int32[M] =
+ *                  the item rows in the order they are handed to workgroups (a permutation of 0..M-1, heaviest row first by
+ *                  sum over its users of their entry counts; any permutation gives the same records).  max_sq = max over
+ *                  items of sum_u m_ua^2 bounds every count: PS_EUNSUPPORTED if it reaches 2^31 (the record's count is an
+ *                  int32).  acc_slots = partners the LDS accumulator holds at once (0 = default, at most 10000); a row with
+ *                  more distinct partners is redone in a global slab of M entries and stays exact.  workspace:
+ *                  ps_cooc_pairs_sparse_workspace_bytes(M, acc_slots) bytes (0 = shape or acc_slots not supported; O(M) plus a
+ *                  bounded number of such slabs: at most 512, at most 2 GiB but at least 4), 8-byte aligned; fewer:
+ *                  PS_EWORKSPACE.  U, M < 2^31, thr >= 1, capacity >= 0, else PS_EINVAL.  Like
+ *                  ps_cooc_pairs it SYNCHRONISES its stream and reports through *count / *h_count, writes the first
+ *                  `capacity` records and returns PS_EWORKSPACE when there are more.
  * ps_cooc_keys   : per record the reference's dict-insertion key (u, p, q): u = the first common user, p < q the first
  *                  positions of a and b in u's group (the first two of a when a == b), as
  *                  keys[k] = (uptr[u] + p) * R + (uptr[u] + q)   (ascending key == the reference's output order).
@@ -381,6 +396,11 @@ int ps_cooc_planes(const int32_t *user, const int32_t *item, const int32_t *mult
                    int max_mult, void *planes, size_t planes_bytes, int64_t *item_stats, int32_t *max_seen, ps_stream_t stream);
 int ps_cooc_pairs(const void *planes, int64_t U, int64_t M, int max_mult, int64_t max_sq, const int64_t *item_stats, int64_t thr,
                   ps_cooc_record *records, int64_t capacity, int64_t *count, int64_t *h_count, ps_stream_t stream);
+size_t ps_cooc_pairs_sparse_workspace_bytes(int64_t M, int acc_slots);
+int ps_cooc_pairs_sparse(const int64_t *iptr, const int32_t *iuser, const int32_t *imult, const int64_t *eptr, const int32_t *eitem,
+                         const int32_t *emult, const int32_t *order, int64_t n, int64_t U, int64_t M, int64_t max_sq, int64_t thr,
+                         int acc_slots, ps_cooc_record *records, int64_t capacity, int64_t *count, int64_t *h_count,
+                         void *workspace, size_t workspace_bytes, ps_stream_t stream);
 int ps_cooc_keys(const ps_cooc_record *records, int64_t n, int64_t U, int64_t M, const int64_t *iptr, const int32_t *iuser,
                  const int32_t *imult, const int64_t *uptr, const int32_t *uitem, const int32_t *upos, int64_t R,
                  int64_t *keys, ps_stream_t stream);

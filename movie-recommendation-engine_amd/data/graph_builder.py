@@ -1,7 +1,9 @@
 """data.graph_builder -- drop-in for the reference module of the same name (reference data/graph_builder.py).
 
 build_item_similarity_graph is the reference's per-user pair loop (one dict update per ordered pair of positions in every
-user's history: ~6.1e9 updates at SYN-25M scale) as an exact integer GEMM on the matrix cores (pinsage_hip.cooc).  Counts,
+user's history: ~6.1e9 updates at SYN-25M scale) as an exact integer GEMM on the matrix cores, or, where that GEMM cannot
+run (a multiplicity above 127, counts beyond its exact range, planes that do not fit), as an exact row-wise sparse product
+(pinsage_hip.cooc, GraphBuilder.cooc_method).  Counts,
 threshold, edge order and dtypes are the reference's: pairs in dict insertion order, each as [a -> b, b -> a] with a <= b,
 weights = counts as float32; CPU tensors are returned and, as in the reference, self.edge_index / self.edge_weight are NOT
 set by it.  build_bipartite_graph and get_adjacency_list are vectorised host versions with the reference's results.
@@ -36,6 +38,8 @@ class GraphBuilder:
     """
     Builds and manipulates graph structures for recommendation systems.
     """
+    cooc_method = "auto"      # producer of the co-occurrence counts: "dense", "sparse" or "auto" (pinsage_hip.cooc)
+
     def __init__(self, dataset):
         self.dataset = dataset
         self.edge_index = None
@@ -75,7 +79,7 @@ class GraphBuilder:
             raise ValueError("movie_id_to_idx holds negative indices")
         dev = nv.require_gpu()
         ei, ew = cooc.item_cooccurrence_graph(torch.from_numpy(np.asarray(users, dtype=np.int64)), torch.from_numpy(items),
-                                              num_items, threshold=threshold, device=dev)
+                                              num_items, threshold=threshold, device=dev, method=self.cooc_method)
         edge_index, edge_weight = ei.cpu(), ew.cpu()
         print(f"Created item similarity graph with {edge_index.size(1) // 2} unique edges")
         return edge_index, edge_weight

@@ -40,7 +40,8 @@ SYMBOLS = [
     "ps_importance_pool", "ps_permute_k", "ps_linear", "ps_gcn_layer_workspace_bytes", "ps_gcn_layer", "ps_lsh_encode", "ps_hamming_topk_workspace_bytes", "ps_hamming_topk",
     "ps_lsh_planes_bytes", "ps_lsh_expand", "ps_hamming_topk_mfma_workspace_bytes", "ps_hamming_topk_mfma", "ps_hamming_topk_mfma_codes",
     "ps_topk_merge", "ps_topk_merge_strided", "ps_dot_topk_workspace_bytes", "ps_dot_topk", "ps_row_dot", "ps_rank_count", "ps_l2_topk_workspace_bytes", "ps_l2_topk", "ps_ivf_topk_workspace_bytes", "ps_ivf_topk", "ps_spmm_csr",
-    "ps_cooc_planes_bytes", "ps_cooc_planes", "ps_cooc_pairs", "ps_cooc_keys", "ps_cooc_emit",
+    "ps_cooc_planes_bytes", "ps_cooc_planes", "ps_cooc_pairs", "ps_cooc_pairs_sparse_workspace_bytes", "ps_cooc_pairs_sparse", "ps_cooc_keys",
+    "ps_cooc_emit",
     "ps_hardest_negative", "ps_margin_loss", "ps_margin_loss_bwd",
 ]
 
@@ -60,7 +61,8 @@ def lib():
         _lib.ps_error_string.restype = C.c_char_p
         for name in ("ps_csr_build_workspace_bytes", "ps_hamming_topk_workspace_bytes", "ps_dot_topk_workspace_bytes",
                      "ps_l2_topk_workspace_bytes", "ps_ivf_topk_workspace_bytes", "ps_mt19937_workspace_bytes", "ps_lsh_planes_bytes",
-                     "ps_hamming_topk_mfma_workspace_bytes", "ps_gcn_layer_workspace_bytes", "ps_cooc_planes_bytes"):
+                     "ps_hamming_topk_mfma_workspace_bytes", "ps_gcn_layer_workspace_bytes", "ps_cooc_planes_bytes",
+                     "ps_cooc_pairs_sparse_workspace_bytes"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = C.c_size_t
     return _lib
