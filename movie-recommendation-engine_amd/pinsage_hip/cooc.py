@@ -129,15 +129,14 @@ def _records_dense(P, thr, capacity, dev, tick):
         raise ValueError(f"a (user, item) pair occurs {P.max_mult} times; the co-occurrence GEMM takes multiplicities up to 127")
     U, M = P.U, P.M
     lib = nv.lib()
-    nbytes = lib.ps_cooc_planes_bytes(nv.i64(U), nv.i64(M), nv.i32(P.max_mult))
+    planes, nbytes = nv.workspace("ps_cooc_planes_bytes", dev, U, M, P.max_mult)
     if nbytes == 0:
         raise ValueError(f"co-occurrence shape not supported (users {U}, items {M})")
-    planes = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     stats = torch.empty(3 * M, dtype=torch.int64, device=dev)
     seen = torch.empty(1, dtype=torch.int32, device=dev)
     st = nv.stream()
-    nv.call("ps_cooc_planes", nv.ptr(P.iuser), nv.ptr(P.iitem), nv.ptr(P.imult), nv.i64(P.iuser.numel()), nv.i64(U), nv.i64(M),
-            nv.i32(P.max_mult), nv.ptr(planes), C.c_size_t(nbytes), nv.ptr(stats), nv.ptr(seen), st)
+    nv.call("ps_cooc_planes", nv.ptr(P.iuser), nv.ptr(P.iitem), nv.ptr(P.imult), P.iuser.numel(), U, M, P.max_mult, nv.ptr(planes),
+            nbytes, nv.ptr(stats), nv.ptr(seen), st)
     max_sq = int(stats[M:2 * M].max())
     if int(seen) != P.max_mult:
         raise nv.NativeError(f"ps_cooc_planes saw multiplicity {int(seen)}, expected {P.max_mult}")
@@ -147,8 +146,8 @@ def _records_dense(P, thr, capacity, dev, tick):
     h_count = C.c_int64(0)
     for attempt in range(2):
         rec = torch.empty((max(cap, 1), 4), dtype=torch.int32, device=dev)
-        rc = lib.ps_cooc_pairs(nv.ptr(planes), nv.i64(U), nv.i64(M), nv.i32(P.max_mult), nv.i64(max_sq), nv.ptr(stats), nv.i64(thr),
-                               nv.ptr(rec), nv.i64(cap), nv.ptr(count), C.byref(h_count), st)
+        rc = lib.ps_cooc_pairs(nv.ptr(planes), U, M, P.max_mult, max_sq, nv.ptr(stats), thr, nv.ptr(rec), cap, nv.ptr(count),
+                               C.byref(h_count), st)
         if rc == nv.PS_EWORKSPACE and attempt == 0:
             cap = int(h_count.value)
             del rec
@@ -168,13 +167,12 @@ def _records_sparse(P, thr, capacity, acc_slots, dev):
     U, M = P.U, P.M
     lib = nv.lib()
     slots = int(acc_slots)
-    nbytes = lib.ps_cooc_pairs_sparse_workspace_bytes(nv.i64(M), nv.i32(slots))
-    if nbytes == 0:
+    if lib.ps_cooc_pairs_sparse_workspace_bytes(M, slots) == 0:
         raise ValueError(f"sparse co-occurrence: items {M} or acc_slots {slots} not supported")
     max_sq = P.max_sq()
     eptr, eitem, emult = P.by_user()
     order = P.row_order()
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws, nbytes = nv.workspace("ps_cooc_pairs_sparse_workspace_bytes", dev, M, slots)
     st = nv.stream()
     cap = _first_capacity(P, capacity, dev)
     count = torch.empty(1, dtype=torch.int64, device=dev)
@@ -182,9 +180,8 @@ def _records_sparse(P, thr, capacity, acc_slots, dev):
     for attempt in range(2):
         rec = torch.empty((max(cap, 1), 4), dtype=torch.int32, device=dev)
         rc = lib.ps_cooc_pairs_sparse(nv.ptr(P.iptr), nv.ptr(P.iuser), nv.ptr(P.imult), nv.ptr(eptr), nv.ptr(eitem), nv.ptr(emult),
-                                      nv.ptr(order), nv.i64(P.iuser.numel()), nv.i64(U), nv.i64(M), nv.i64(max_sq), nv.i64(thr),
-                                      nv.i32(slots), nv.ptr(rec), nv.i64(cap), nv.ptr(count), C.byref(h_count), nv.ptr(ws),
-                                      C.c_size_t(nbytes), st)
+                                      nv.ptr(order), P.iuser.numel(), U, M, max_sq, thr, slots, nv.ptr(rec), cap, nv.ptr(count),
+                                      C.byref(h_count), nv.ptr(ws), nbytes, st)
         if rc == nv.PS_EWORKSPACE and attempt == 0:
             cap = int(h_count.value)
             del rec
@@ -201,7 +198,7 @@ def _auto_method(P, dev):
     """dense wherever dense can run, sparse otherwise (no choice by speed)"""
     if P.max_mult > 127 or P.max_sq() >= _dense_exact_range(P.max_mult):
         return "sparse"
-    nbytes = nv.lib().ps_cooc_planes_bytes(nv.i64(P.U), nv.i64(P.M), nv.i32(P.max_mult))
+    nbytes = nv.lib().ps_cooc_planes_bytes(P.U, P.M, P.max_mult)
     return "dense" if nbytes != 0 and _dense_fits(nbytes, dev) else "sparse"
 
 
@@ -237,8 +234,8 @@ def item_cooccurrence_graph(user_ids, item_idx, num_items, threshold=5, device="
     st = nv.stream()
     tick("pairs")
     keys = torch.empty(n, dtype=torch.int64, device=dev)
-    nv.call("ps_cooc_keys", nv.ptr(rec), nv.i64(n), nv.i64(U), nv.i64(M), nv.ptr(P.iptr), nv.ptr(P.iuser), nv.ptr(P.imult),
-            nv.ptr(P.uptr), nv.ptr(P.uitem), nv.ptr(P.upos), nv.i64(R), nv.ptr(keys), st)
+    nv.call("ps_cooc_keys", nv.ptr(rec), n, U, M, nv.ptr(P.iptr), nv.ptr(P.iuser), nv.ptr(P.imult), nv.ptr(P.uptr), nv.ptr(P.uitem),
+            nv.ptr(P.upos), R, nv.ptr(keys), st)
     tick("keys")
     if n and int(keys.min()) < 0:
         raise nv.NativeError("ps_cooc_keys found no first common user for some pair")
@@ -246,6 +243,6 @@ def item_cooccurrence_graph(user_ids, item_idx, num_items, threshold=5, device="
     del keys
     edge_index = torch.empty((2, 2 * n), dtype=torch.int64, device=dev)
     edge_weight = torch.empty(2 * n, dtype=torch.float32, device=dev)
-    nv.call("ps_cooc_emit", nv.ptr(rec), nv.ptr(perm), nv.i64(n), nv.ptr(edge_index), nv.ptr(edge_weight), st)
+    nv.call("ps_cooc_emit", nv.ptr(rec), nv.ptr(perm), n, nv.ptr(edge_index), nv.ptr(edge_weight), st)
     tick("order")
     return edge_index, edge_weight

@@ -18,21 +18,13 @@ def _rowmajor(w):
         raise ValueError("2-D matrix expected")
     if w.stride(1) != 1 or w.stride(0) < w.size(1):
         w = w.contiguous()
-    return w, int(w.stride(0)) if w.size(0) > 1 else max(int(w.stride(0)), int(w.size(1)))
+    return w, w.stride(0) if w.size(0) > 1 else max(w.stride(0), w.size(1))
 
 
 def _require_cuda(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:
             raise nv.NativeError("libpinsage_hip takes device (HBM) tensors; got a CPU tensor (no CPU fallback)")
-
-
-def _ptr_view(t):
-    if t is None:
-        return nv.C.c_void_p(0)
-    if not t.is_cuda:
-        raise nv.NativeError("device tensor expected")
-    return nv.C.c_void_p(t.data_ptr())
 
 
 class StagedWeight:
@@ -54,12 +46,12 @@ def stage_weight(W):
     if isinstance(W, StagedWeight) or W is None:
         return W
     _require_cuda(W)
-    if W.dim() != 2 or W.dtype != torch.float32 or int(W.size(1)) % 32 != 0:
+    if W.dim() != 2 or W.dtype != torch.float32 or W.size(1) % 32 != 0:
         return W
     Wk, ld = _rowmajor(W)
-    out = torch.empty((int(Wk.size(0)), int(Wk.size(1))), dtype=torch.float32, device=W.device)
+    out = torch.empty((Wk.size(0), Wk.size(1)), dtype=torch.float32, device=W.device)
     with torch.cuda.device(W.device):
-        nv.call("ps_permute_k", _ptr_view(Wk), nv.i64(int(Wk.size(0))), nv.i32(int(Wk.size(1))), nv.i32(ld), nv.ptr(out), nv.stream())
+        nv.call("ps_permute_k", nv.ptr(Wk, contiguous=False), Wk.size(0), Wk.size(1), ld, nv.ptr(out), nv.stream())
     return StagedWeight(out)
 
 
@@ -76,26 +68,25 @@ def linear(x, W, b=None, x2=None, W2=None, relu=False, l2norm=False):
     x = x.contiguous()
     if x.dtype != torch.float32:
         raise TypeError("fp32 expected")
-    M, K = int(x.size(0)), int(x.size(1))
+    M, K = x.size(0), x.size(1)
     Wk, ldw = _rowmajor(W)
-    N = int(Wk.size(0))
-    if int(Wk.size(1)) != K:
+    N = Wk.size(0)
+    if Wk.size(1) != K:
         raise ValueError(f"shape mismatch: x [{M},{K}] vs W {tuple(Wk.shape)}")
     K2, ldw2, W2k = 0, 0, None
     if x2 is not None:
         x2 = x2.contiguous()
         W2k, ldw2 = _rowmajor(W2)
-        K2 = int(x2.size(1))
-        if int(W2k.size(1)) != K2 or int(W2k.size(0)) != N or int(x2.size(0)) != M:
+        K2 = x2.size(1)
+        if W2k.size(1) != K2 or W2k.size(0) != N or x2.size(0) != M:
             raise ValueError("shape mismatch in the second operand pair")
     if b is not None:
         b = b.contiguous()
     y = torch.empty((M, N), dtype=torch.float32, device=x.device)
     flags = (nv.PS_RELU if relu else 0) | (nv.PS_L2NORM if l2norm else 0) | (nv.PS_WPERM if staged else 0)
     with torch.cuda.device(x.device):
-        nv.call("ps_linear", nv.ptr(x), nv.i64(M), nv.i32(K), _ptr_view(Wk), nv.i32(ldw), nv.ptr(b), nv.i32(N),
-                                    nv.ptr(x2), nv.i32(K2), _ptr_view(W2k), nv.i32(ldw2), nv.i32(flags), nv.ptr(y),
-                                    nv.stream())
+        nv.call("ps_linear", nv.ptr(x), M, K, nv.ptr(Wk, contiguous=False), ldw, nv.ptr(b), N, nv.ptr(x2), K2,
+                nv.ptr(W2k, contiguous=False), ldw2, flags, nv.ptr(y), nv.stream())
     return y
 
 
@@ -113,14 +104,13 @@ def gcn_layer(x, W, b, h_full, ids, counts, nvalid, W2, wts=None, max_idx=None, 
     x, h_full = x.contiguous(), h_full.contiguous()
     if x.dtype != torch.float32 or h_full.dtype != torch.float32:
         raise TypeError("fp32 expected")
-    M, K = int(x.size(0)), int(x.size(1))
-    n_full, H = int(h_full.size(0)), int(h_full.size(1))
+    M, K, n_full, H = x.size(0), x.size(1), h_full.size(0), h_full.size(1)
     Wk, ldw = _rowmajor(Wm)
     W2k, ldw2 = _rowmajor(W2m)
-    N = int(Wk.size(0))
-    if int(Wk.size(1)) != K or int(W2k.size(1)) != H or int(W2k.size(0)) != N or int(ids.size(0)) != M:
+    N = Wk.size(0)
+    if Wk.size(1) != K or W2k.size(1) != H or W2k.size(0) != N or ids.size(0) != M:
         raise ValueError("shape mismatch")
-    T = int(ids.size(1))
+    T = ids.size(1)
     if max_idx is None:
         max_idx = n_full - 1
     if b is not None:
@@ -129,16 +119,13 @@ def gcn_layer(x, W, b, h_full, ids, counts, nvalid, W2, wts=None, max_idx=None, 
     counts = counts.contiguous() if counts is not None else None
     wts = wts.contiguous() if wts is not None else None
     flags = (nv.PS_RELU if relu else 0) | (nv.PS_L2NORM if l2norm else 0) | (nv.PS_WPERM if staged else 0)
-    L = nv.lib()
-    wsb = int(L.ps_gcn_layer_workspace_bytes(nv.i64(M), nv.i32(H)))
+    ws, wsb = nv.workspace("ps_gcn_layer_workspace_bytes", x.device, M, H)
     if wsb > 0:
         y = torch.empty((M, N), dtype=torch.float32, device=x.device)
-        ws = torch.empty((wsb,), dtype=torch.uint8, device=x.device)
         with torch.cuda.device(x.device):
-            rc = L.ps_gcn_layer(nv.ptr(x), nv.i64(M), nv.i32(K), _ptr_view(Wk), nv.i32(ldw), nv.ptr(b), nv.i32(N), nv.ptr(h_full),
-                                nv.i64(n_full), nv.i32(H), nv.ptr(ids), nv.ptr(counts), nv.ptr(wts), nv.ptr(nvalid), nv.i32(T),
-                                nv.i64(int(max_idx)), nv.i32(int(renorm)), _ptr_view(W2k), nv.i32(ldw2), nv.i32(flags), nv.ptr(y),
-                                nv.ptr(ws), nv.C.c_size_t(wsb), nv.stream())
+            rc = nv.lib().ps_gcn_layer(nv.ptr(x), M, K, nv.ptr(Wk, contiguous=False), ldw, nv.ptr(b), N, nv.ptr(h_full), n_full, H,
+                                       nv.ptr(ids), nv.ptr(counts), nv.ptr(wts), nv.ptr(nvalid), T, int(max_idx), int(renorm),
+                                       nv.ptr(W2k, contiguous=False), ldw2, flags, nv.ptr(y), nv.ptr(ws), wsb, nv.stream())
         if rc != nv.PS_EUNSUPPORTED:
             nv.check(rc, "ps_gcn_layer")
             return y
@@ -154,14 +141,13 @@ def lsh_encode(x, A):
     _require_cuda(x, A)
     x = x.contiguous()
     A = A.contiguous()
-    n, d = int(x.size(0)), int(x.size(1))
-    nbits = int(A.size(0))
-    if int(A.size(1)) != d:
+    n, d = x.size(0), x.size(1)
+    nbits = A.size(0)
+    if A.size(1) != d:
         raise ValueError("projection matrix must be [nbits, dim]")
     codes = torch.empty((n, nbits // 8), dtype=torch.uint8, device=x.device)
     with torch.cuda.device(x.device):
-        nv.call("ps_lsh_encode", nv.ptr(x), nv.i64(n), nv.i32(d), nv.ptr(A), nv.i32(nbits), nv.ptr(codes),
-                                        nv.i32(nv.PS_WPERM if staged else 0), nv.stream())
+        nv.call("ps_lsh_encode", nv.ptr(x), n, d, nv.ptr(A), nbits, nv.ptr(codes), nv.PS_WPERM if staged else 0, nv.stream())
     return codes
 
 
@@ -173,18 +159,16 @@ def lsh_expand(codes):
     None when the code size is not a multiple of 4 bytes."""
     _require_cuda(codes)
     codes = codes.contiguous()
-    n, cs = int(codes.size(0)), int(codes.size(1))
-    nb = int(nv.lib().ps_lsh_planes_bytes(nv.i64(n), nv.i32(cs)))
-    if nb == 0:
-        return None
-    planes = torch.empty(nb, dtype=torch.uint8, device=codes.device)
-    with torch.cuda.device(codes.device):
-        nv.call("ps_lsh_expand", nv.ptr(codes), nv.i64(n), nv.i32(cs), nv.ptr(planes), nv.stream())
+    n, cs = codes.size(0), codes.size(1)
+    planes, nb = nv.workspace("ps_lsh_planes_bytes", codes.device, n, cs)
+    if nb:
+        with torch.cuda.device(codes.device):
+            nv.call("ps_lsh_expand", nv.ptr(codes), n, cs, nv.ptr(planes), nv.stream())
     return planes
 
 
 def hamming_mfma_supported(nq, N, cs, k):
-    return int(nv.lib().ps_hamming_topk_mfma_workspace_bytes(nv.i64(nq), nv.i64(N), nv.i32(cs), nv.i32(k))) > 0
+    return nv.lib().ps_hamming_topk_mfma_workspace_bytes(nq, N, cs, k) > 0
 
 
 def hamming_topk(qcodes, codes, k, id_offset=0, planes=None, use_mfma=True, out=None):
@@ -196,8 +180,8 @@ def hamming_topk(qcodes, codes, k, id_offset=0, planes=None, use_mfma=True, out=
     _require_cuda(qcodes, codes)
     qcodes = qcodes.contiguous()
     codes = codes.contiguous()
-    nq, cs = int(qcodes.size(0)), int(qcodes.size(1))
-    N = int(codes.size(0))
+    nq, cs = qcodes.size(0), qcodes.size(1)
+    N = codes.size(0)
     if out is not None:
         dist, ids = out
         if (tuple(dist.shape) != (nq, k) or tuple(ids.shape) != (nq, k) or dist.dtype != torch.int32
@@ -214,23 +198,18 @@ def hamming_topk(qcodes, codes, k, id_offset=0, planes=None, use_mfma=True, out=
     if out is None:
         dist = torch.empty((nq, k), dtype=torch.int32, device=qcodes.device)
         ids = torch.empty((nq, k), dtype=torch.int64, device=qcodes.device)
-    L = nv.lib()
     if use_mfma and planes is not None:
-        wsb = int(L.ps_hamming_topk_mfma_workspace_bytes(nv.i64(nq), nv.i64(N), nv.i32(cs), nv.i32(k)))
+        ws, wsb = nv.workspace("ps_hamming_topk_mfma_workspace_bytes", qcodes.device, nq, N, cs, k)
         if wsb > 0:
-            ws = torch.empty(wsb, dtype=torch.uint8, device=qcodes.device)
             with torch.cuda.device(qcodes.device):
                 # the queries go in as packed codes: the scan's workgroups build their own sign planes
-                nv.call("ps_hamming_topk_mfma_codes", nv.ptr(qcodes), nv.i64(nq), nv.ptr(planes), nv.i64(N), nv.i32(cs),
-                        nv.i32(k), nv.i64(id_offset), nv.ptr(dist), nv.ptr(ids), nv.ptr(ws), nv.C.c_size_t(wsb),
-                        nv.stream())
+                nv.call("ps_hamming_topk_mfma_codes", nv.ptr(qcodes), nq, nv.ptr(planes), N, cs, k, id_offset, nv.ptr(dist),
+                        nv.ptr(ids), nv.ptr(ws), wsb, nv.stream())
             return dist, ids
-    wsb = int(L.ps_hamming_topk_workspace_bytes(nv.i64(nq), nv.i64(N), nv.i32(cs), nv.i32(k)))
-    ws = torch.empty(wsb, dtype=torch.uint8, device=qcodes.device)
+    ws, wsb = nv.workspace("ps_hamming_topk_workspace_bytes", qcodes.device, nq, N, cs, k)
     with torch.cuda.device(qcodes.device):
-        nv.call("ps_hamming_topk", nv.ptr(qcodes), nv.i64(nq), nv.ptr(codes) if N else nv.C.c_void_p(0), nv.i64(N),
-                                   nv.i32(cs), nv.i32(k), nv.i64(id_offset), nv.ptr(dist), nv.ptr(ids), nv.ptr(ws),
-                                   nv.C.c_size_t(wsb), nv.stream())
+        nv.call("ps_hamming_topk", nv.ptr(qcodes), nq, nv.ptr(codes if N else None), N, cs, k, id_offset, nv.ptr(dist),
+                nv.ptr(ids), nv.ptr(ws), wsb, nv.stream())
     return dist, ids
 
 
@@ -249,7 +228,7 @@ def _hamming_topk_large_k(qcodes, codes, k, id_offset):
     -- small integers, exact in fp32 -- so the exact L2 search (ps_l2_topk: fp32-MFMA GEMM + multi-sweep row top-k, any k,
     ties by id) returns the same (distance, id) order as the scans.  Costs a float image of the table (2 KiB per 512-bit
     code): meant for the occasional large request, not for the hot path."""
-    N, nbits = int(codes.size(0)), int(codes.size(1)) * 8
+    N, nbits = codes.size(0), codes.size(1) * 8
     if N * nbits * 4 > LARGE_K_SIGN_BYTES:
         raise ValueError(f"LSH search with k = {k} > {HAMMING_MAX_K} expands the code table to floats "
                          f"({N * nbits * 4 / 2 ** 30:.1f} GiB here, limit {LARGE_K_SIGN_BYTES >> 30} GiB): split the table or the request")
@@ -265,12 +244,11 @@ def topk_merge(dist_in, ids_in):
     """[P, nq, k] candidate lists -> global [nq, k] by (distance, id)."""
     dist_in = dist_in.contiguous()
     ids_in = ids_in.contiguous()
-    P, nq, k = [int(v) for v in dist_in.shape]
+    P, nq, k = dist_in.shape
     dist = torch.empty((nq, k), dtype=torch.int32, device=dist_in.device)
     ids = torch.empty((nq, k), dtype=torch.int64, device=dist_in.device)
     with torch.cuda.device(dist_in.device):
-        nv.call("ps_topk_merge", nv.ptr(dist_in), nv.ptr(ids_in), nv.i32(P), nv.i64(nq), nv.i32(k), nv.ptr(dist),
-                                        nv.ptr(ids), nv.stream())
+        nv.call("ps_topk_merge", nv.ptr(dist_in), nv.ptr(ids_in), P, nq, k, nv.ptr(dist), nv.ptr(ids), nv.stream())
     return dist, ids
 
 
@@ -279,16 +257,16 @@ def topk_merge_records(records, nq, k):
     as one all-gather delivers them -> global (dist int32[nq,k], ids int64[nq,k]) by (distance, id); no repacking."""
     if records.dtype != torch.uint8 or records.dim() != 2 or not records.is_contiguous():
         raise ValueError("records must be a contiguous uint8 [P, record_bytes] tensor")
-    P, rec = int(records.size(0)), int(records.size(1))
-    n = int(nq) * int(k)
+    P, rec = records.shape
+    nq, k = int(nq), int(k)
+    n = nq * k
     if rec < 12 * n or rec % 8 != 0:
         raise ValueError("record too short or not 8-byte aligned")
     dist = torch.empty((nq, k), dtype=torch.int32, device=records.device)
     ids = torch.empty((nq, k), dtype=torch.int64, device=records.device)
     base = records.data_ptr()
     with torch.cuda.device(records.device):
-        nv.call("ps_topk_merge_strided", nv.C.c_void_p(base + 8 * n), nv.i64(rec // 4), nv.C.c_void_p(base), nv.i64(rec // 8),
-                nv.i32(P), nv.i64(int(nq)), nv.i32(int(k)), nv.ptr(dist), nv.ptr(ids), nv.stream())
+        nv.call("ps_topk_merge_strided", base + 8 * n, rec // 4, base, rec // 8, P, nq, k, nv.ptr(dist), nv.ptr(ids), nv.stream())
     return dist, ids
 
 
@@ -296,19 +274,16 @@ def dot_topk(E, qidx, k, exclude_self=True):
     """Exact search: top-k of E[q] @ E.T per query row index (reference inference.py:112-118)."""
     E = E.contiguous()
     qidx = qidx.to(device=E.device, dtype=torch.int64).contiguous()
-    N, D = int(E.size(0)), int(E.size(1))
-    nq = int(qidx.numel())
+    N, D = E.size(0), E.size(1)
+    nq = qidx.numel()
     if k < 1:
         raise ValueError(f"k must be positive, got {k}")
     vals = torch.empty((nq, k), dtype=torch.float32, device=E.device)
     ids = torch.empty((nq, k), dtype=torch.int64, device=E.device)
-    L = nv.lib()
-    wsb = int(L.ps_dot_topk_workspace_bytes(nv.i64(nq), nv.i64(N), nv.i32(D), nv.i32(k)))
-    ws = torch.empty(wsb, dtype=torch.uint8, device=E.device)
+    ws, wsb = nv.workspace("ps_dot_topk_workspace_bytes", E.device, nq, N, D, k)
     with torch.cuda.device(E.device):
-        nv.call("ps_dot_topk", nv.ptr(E), nv.i64(N), nv.i32(D), nv.ptr(qidx), nv.i64(nq), nv.i32(k),
-                               nv.i32(int(exclude_self)), nv.ptr(vals), nv.ptr(ids), nv.ptr(ws), nv.C.c_size_t(wsb),
-                               nv.stream())
+        nv.call("ps_dot_topk", nv.ptr(E), N, D, nv.ptr(qidx), nq, k, int(exclude_self), nv.ptr(vals), nv.ptr(ids), nv.ptr(ws), wsb,
+                nv.stream())
     return vals, ids
 
 
@@ -323,16 +298,16 @@ def row_dot(A, ia, B, ib):
     """out[i] = A[ia[i]] . B[ib[i]] (ps_row_dot): the arithmetic of linear() / dot_topk(), so out[i] is bit-identical to the
     entry linear(A[ia], B)[i, ib[i]].  An index outside the matrix gives NaN."""
     A, B = _fp32_rows(A), _fp32_rows(B)
-    if int(A.size(1)) != int(B.size(1)):
+    if A.size(1) != B.size(1):
         raise ValueError(f"shape mismatch: A {tuple(A.shape)} vs B {tuple(B.shape)}")
     ia = ia.to(device=A.device, dtype=torch.int64).contiguous()
     ib = ib.to(device=A.device, dtype=torch.int64).contiguous()
     if ia.numel() != ib.numel():
         raise ValueError("ia and ib must have the same length")
-    out = torch.empty(int(ia.numel()), dtype=torch.float32, device=A.device)
+    out = torch.empty(ia.numel(), dtype=torch.float32, device=A.device)
     with torch.cuda.device(A.device):
-        nv.call("ps_row_dot", nv.ptr(A), nv.i64(int(A.size(0))), nv.ptr(B), nv.i64(int(B.size(0))), nv.i32(int(A.size(1))),
-                nv.ptr(ia), nv.ptr(ib), nv.i64(int(ia.numel())), nv.ptr(out), nv.stream())
+        nv.call("ps_row_dot", nv.ptr(A), A.size(0), nv.ptr(B), B.size(0), A.size(1), nv.ptr(ia), nv.ptr(ib), ia.numel(), nv.ptr(out),
+                nv.stream())
     return out
 
 
@@ -341,20 +316,20 @@ def rank_count(E, Q, thr, tid, id_offset=0, count=None):
     (ps_rank_count: similarity descending by float key, ties by ascending id).  One GEMM with a counting epilogue, no [nq, N]
     slab.  count: int64 [nq] on the device (a new zero vector when None); calls over disjoint item ranges add up."""
     E, Q = _fp32_rows(E), _fp32_rows(Q)
-    if int(E.size(1)) != int(Q.size(1)):
+    if E.size(1) != Q.size(1):
         raise ValueError(f"shape mismatch: E {tuple(E.shape)} vs Q {tuple(Q.shape)}")
-    nq = int(Q.size(0))
+    nq = Q.size(0)
     thr = thr.to(device=Q.device, dtype=torch.float32).contiguous()
     tid = tid.to(device=Q.device, dtype=torch.int64).contiguous()
-    if int(thr.numel()) != nq or int(tid.numel()) != nq:
+    if thr.numel() != nq or tid.numel() != nq:
         raise ValueError("thr and tid need one entry per query row")
     if count is None:
         count = torch.zeros(nq, dtype=torch.int64, device=Q.device)
-    elif count.dtype != torch.int64 or not count.is_contiguous() or int(count.numel()) != nq or count.device != Q.device:
+    elif count.dtype != torch.int64 or not count.is_contiguous() or count.numel() != nq or count.device != Q.device:
         raise ValueError("count must be a contiguous int64 [nq] tensor on the queries' device")
     with torch.cuda.device(Q.device):
-        nv.call("ps_rank_count", nv.ptr(E), nv.i64(int(E.size(0))), nv.i32(int(E.size(1))), nv.i64(int(id_offset)), nv.ptr(Q),
-                nv.i64(nq), nv.ptr(thr), nv.ptr(tid), nv.ptr(count), nv.stream())
+        nv.call("ps_rank_count", nv.ptr(E), E.size(0), E.size(1), int(id_offset), nv.ptr(Q), nq, nv.ptr(thr), nv.ptr(tid),
+                nv.ptr(count), nv.stream())
     return count
 
 
@@ -368,7 +343,7 @@ def target_rank(E, qidx, gt, id_offset=0):
     gt = gt.to(device=E.device, dtype=torch.int64).contiguous()
     if qidx.numel() != gt.numel():
         raise ValueError("qidx and gt must have the same length")
-    N = int(E.size(0))
+    N = E.size(0)
     for name, t in (("qidx", qidx), ("gt", gt)):
         if t.numel() and (int(t.min()) < 0 or int(t.max()) >= N):
             raise IndexError(f"{name} holds a row index outside [0, {N})")
@@ -382,19 +357,17 @@ def l2_topk(X, Q, k, assign=None, probe=None):
     """k nearest by squared L2 (IndexFlatL2 / IndexIVFFlat scan): -> (dist fp32[nq,k], ids int64[nq,k])."""
     X = X.contiguous()
     Q = Q.to(X.device).contiguous()
-    N, D = int(X.size(0)), int(X.size(1))
-    nq = int(Q.size(0))
+    N, D = X.size(0), X.size(1)
+    nq = Q.size(0)
     if k < 1:
         raise ValueError(f"k must be positive, got {k}")
     dist = torch.empty((nq, k), dtype=torch.float32, device=X.device)
     ids = torch.empty((nq, k), dtype=torch.int64, device=X.device)
-    L = nv.lib()
-    wsb = int(L.ps_l2_topk_workspace_bytes(nv.i64(nq), nv.i64(N), nv.i32(D), nv.i32(k)))
-    ws = torch.empty(wsb, dtype=torch.uint8, device=X.device)
-    words = int(probe.size(1)) if probe is not None else 0
+    ws, wsb = nv.workspace("ps_l2_topk_workspace_bytes", X.device, nq, N, D, k)
+    words = probe.size(1) if probe is not None else 0
     with torch.cuda.device(X.device):
-        nv.call("ps_l2_topk", nv.ptr(X), nv.i64(N), nv.i32(D), nv.ptr(Q), nv.i64(nq), nv.i32(k), nv.ptr(assign),
-                nv.ptr(probe), nv.i32(words), nv.ptr(dist), nv.ptr(ids), nv.ptr(ws), nv.C.c_size_t(wsb), nv.stream())
+        nv.call("ps_l2_topk", nv.ptr(X), N, D, nv.ptr(Q), nq, k, nv.ptr(assign), nv.ptr(probe), words, nv.ptr(dist), nv.ptr(ids),
+                nv.ptr(ws), wsb, nv.stream())
     return dist, ids
 
 
@@ -407,23 +380,21 @@ def ivf_topk(Xs, list_ptr, item_ids, Q, probes, k, max_list=None):
     probes = probes.to(device=Xs.device, dtype=torch.int32).contiguous()
     list_ptr = list_ptr.to(device=Xs.device, dtype=torch.int64).contiguous()
     item_ids = item_ids.to(device=Xs.device, dtype=torch.int64).contiguous()
-    N, D = int(Xs.size(0)), int(Xs.size(1))
-    nq, nprobe, nlist = int(Q.size(0)), int(probes.size(1)), int(list_ptr.numel()) - 1
+    N, D = Xs.size(0), Xs.size(1)
+    nq, nprobe, nlist = Q.size(0), probes.size(1), list_ptr.numel() - 1
     if k < 1:
         raise ValueError(f"k must be positive, got {k}")
-    if int(probes.size(0)) != nq or int(item_ids.numel()) != N or int(Q.size(1)) != D:
+    if probes.size(0) != nq or item_ids.numel() != N or Q.size(1) != D:
         raise ValueError("shape mismatch")
     if max_list is None:
-        max_list = int((list_ptr[1:] - list_ptr[:-1]).max().item()) if nlist else 0
+        max_list = (list_ptr[1:] - list_ptr[:-1]).max().item() if nlist else 0
+    max_list, k = int(max_list), int(k)
     dist = torch.empty((nq, k), dtype=torch.float32, device=Xs.device)
     ids = torch.empty((nq, k), dtype=torch.int64, device=Xs.device)
-    L = nv.lib()
-    wsb = int(L.ps_ivf_topk_workspace_bytes(nv.i64(nq), nv.i64(N), nv.i32(D), nv.i32(k), nv.i32(nlist), nv.i32(nprobe), nv.i64(int(max_list))))
-    ws = torch.empty(wsb, dtype=torch.uint8, device=Xs.device)
+    ws, wsb = nv.workspace("ps_ivf_topk_workspace_bytes", Xs.device, nq, N, D, k, nlist, nprobe, max_list)
     with torch.cuda.device(Xs.device):
-        nv.call("ps_ivf_topk", nv.ptr(Xs), nv.i64(N), nv.i32(D), nv.ptr(list_ptr), nv.i32(nlist), nv.i64(int(max_list)), nv.ptr(item_ids),
-                nv.ptr(Q), nv.i64(nq), nv.ptr(probes), nv.i32(nprobe), nv.i32(int(k)), nv.ptr(dist), nv.ptr(ids), nv.ptr(ws),
-                nv.C.c_size_t(wsb), nv.stream())
+        nv.call("ps_ivf_topk", nv.ptr(Xs), N, D, nv.ptr(list_ptr), nlist, max_list, nv.ptr(item_ids), nv.ptr(Q), nq, nv.ptr(probes),
+                nprobe, k, nv.ptr(dist), nv.ptr(ids), nv.ptr(ws), wsb, nv.stream())
     return dist, ids
 
 
@@ -447,7 +418,7 @@ def _radix_polys(dev):
     if key not in _radix_polys_dev:
         from . import mtjump
         import numpy as np
-        cl2 = int(nv.lib().ps_mt19937_chunk_log2())
+        cl2 = nv.lib().ps_mt19937_chunk_log2()
         _radix_polys_dev[key] = torch.from_numpy(mtjump.radix_polynomials(cl2).view(np.int32)).to(dev).contiguous()
     return _radix_polys_dev[key]
 
@@ -460,8 +431,7 @@ def _window_polys(dev):
     if key not in _window_polys_dev:
         from . import mtjump
         import numpy as np
-        cl2 = int(nv.lib().ps_mt19937_chunk_log2())
-        shift = int(nv.lib().ps_mt19937_window_shift())
+        cl2, shift = nv.lib().ps_mt19937_chunk_log2(), nv.lib().ps_mt19937_window_shift()
         _window_polys_dev[key] = torch.from_numpy(mtjump.window_polynomials(cl2, shift=shift).view(np.int32)).to(dev).contiguous()
     return _window_polys_dev[key]
 
@@ -505,14 +475,12 @@ def mt19937_random_sample(n, device, skip=0, advance=True, parallel=True, radix=
     pos_out = torch.empty(1, dtype=torch.int32, device=dev)
     if raw and (skip != 0 or not parallel or n < (1 << 17)):
         raise ValueError("raw stream: skip = 0, the parallel generator and n >= 2^17 are required")
-    out = (torch.empty(2 * int(n) + 1248, dtype=torch.int32, device=dev) if raw else
-           torch.empty(int(n), dtype=torch.float64, device=dev))
+    n, skip, pos = int(n), int(skip), int(pos)
+    out = torch.empty(2 * n + 1248, dtype=torch.int32, device=dev) if raw else torch.empty(n, dtype=torch.float64, device=dev)
     polys = _jump_polys(dev) if parallel else None
     rpolys = _radix_polys(dev) if (parallel and radix) else None      # radix=False: windows by doubling
     wpolys = _window_polys(dev) if (parallel and radix and one_round) else None    # one_round=False: two radix-32 rounds
-    L = nv.lib()
-    wsb = int(L.ps_mt19937_workspace_bytes(nv.i64(int(skip)), nv.i64(int(n)))) if parallel else 0
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if parallel else None
+    ws, wsb = nv.workspace("ps_mt19937_workspace_bytes", dev, skip, n) if parallel else (None, 0)
     if ranges is not None and not raw:
         raise ValueError("ranges: raw stream only")
     rg = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(-1, 2)) if ranges is not None and len(ranges) else None
@@ -523,20 +491,15 @@ def mt19937_random_sample(n, device, skip=0, advance=True, parallel=True, radix=
         # block that still holds a same-seed stream from an earlier call -- a kernel that read outside its runs would then see
         # correct-looking words.  Poisoned, any such read changes the sampled ids deterministically.
         out.fill_(-1)
+    levels, rlevels, nwin = (0 if t is None else t.size(0) for t in (polys, rpolys, wpolys))
     with torch.cuda.device(dev):
         if raw:
-            nv.call("ps_mt19937_raw_stream", nv.ptr(st_in), nv.i32(int(pos)), nv.i64(int(n)), nv.ptr(out), nv.ptr(st_out),
-                    nv.ptr(pos_out), nv.ptr(polys), nv.i32(int(polys.size(0))), nv.ptr(rpolys),
-                    nv.i32(int(rpolys.size(0)) if rpolys is not None else 0), nv.ptr(wpolys),
-                    nv.i32(int(wpolys.size(0)) if wpolys is not None else 0),
-                    rg.ctypes.data_as(nv.C.c_void_p) if rg is not None else nv.C.c_void_p(0), nv.i32(int(rg.shape[0]) if rg is not None else 0),
-                    nv.ptr(ws), nv.C.c_size_t(wsb), nv.stream())
+            nv.call("ps_mt19937_raw_stream", nv.ptr(st_in), pos, n, nv.ptr(out), nv.ptr(st_out), nv.ptr(pos_out), nv.ptr(polys),
+                    levels, nv.ptr(rpolys), rlevels, nv.ptr(wpolys), nwin, rg.ctypes.data if rg is not None else None,
+                    rg.shape[0] if rg is not None else 0, nv.ptr(ws), wsb, nv.stream())
         else:
-          nv.call("ps_mt19937_random_sample", nv.ptr(st_in), nv.i32(int(pos)), nv.i64(int(skip)), nv.i64(int(n)),
-                nv.ptr(out), nv.ptr(st_out), nv.ptr(pos_out), nv.ptr(polys),
-                nv.i32(int(polys.size(0)) if polys is not None else 0), nv.ptr(rpolys),
-                nv.i32(int(rpolys.size(0)) if rpolys is not None else 0), nv.ptr(wpolys),
-                nv.i32(int(wpolys.size(0)) if wpolys is not None else 0), nv.ptr(ws), nv.C.c_size_t(wsb), nv.stream())
+            nv.call("ps_mt19937_random_sample", nv.ptr(st_in), pos, skip, n, nv.ptr(out), nv.ptr(st_out), nv.ptr(pos_out),
+                    nv.ptr(polys), levels, nv.ptr(rpolys), rlevels, nv.ptr(wpolys), nwin, nv.ptr(ws), wsb, nv.stream())
     if advance == "defer":
         finish_rng_state()                                           # at most one hand-back in flight
         host_state = torch.empty(624, dtype=torch.int32).pin_memory()

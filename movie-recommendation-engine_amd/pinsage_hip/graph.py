@@ -43,23 +43,19 @@ class DeviceGraph:
         self.col = torch.empty(E, dtype=torch.int32, device=dev)
         self.cdf = torch.empty(E, dtype=torch.float64, device=dev)
         wsorted = torch.empty(E, dtype=torch.float64, device=dev)
-        L = nv.lib()
-        ws_bytes = int(L.ps_csr_build_workspace_bytes(nv.i64(E), nv.i64(V)))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws, ws_bytes = nv.workspace("ps_csr_build_workspace_bytes", dev, E, V)
         with torch.cuda.device(dev):
-            nv.call("ps_csr_build", nv.ptr(src), nv.ptr(dst), nv.ptr(w), nv.i64(E), nv.i64(V), nv.ptr(self.rowptr),
-                                    nv.ptr(self.col), nv.ptr(wsorted), nv.ptr(ws), nv.C.c_size_t(ws_bytes), nv.stream())
-            nv.call("ps_cdf_build", nv.ptr(self.rowptr), nv.ptr(wsorted), nv.i64(V), nv.ptr(self.cdf), nv.stream())
+            nv.call("ps_csr_build", nv.ptr(src), nv.ptr(dst), nv.ptr(w), E, V, nv.ptr(self.rowptr), nv.ptr(self.col),
+                    nv.ptr(wsorted), nv.ptr(ws), ws_bytes, nv.stream())
+            nv.call("ps_cdf_build", nv.ptr(self.rowptr), nv.ptr(wsorted), V, nv.ptr(self.cdf), nv.stream())
             # exact lookup accelerators for the walk kernels: packed (row start, degree) + bucket table
             self.nodeinfo = torch.empty(2 * V, dtype=torch.int32, device=dev)
             self.guide = torch.empty(E, dtype=torch.int32, device=dev)
             if E:
-                nv.call("ps_guide_build", nv.ptr(self.rowptr), nv.ptr(self.cdf), nv.i64(V), nv.ptr(self.nodeinfo),
-                        nv.ptr(self.guide), nv.stream())
+                nv.call("ps_guide_build", nv.ptr(self.rowptr), nv.ptr(self.cdf), V, nv.ptr(self.nodeinfo), nv.ptr(self.guide), nv.stream())
             self.packed = torch.empty(((E + 7) // 8) * 128, dtype=torch.uint8, device=dev)
             if E:
-                nv.call("ps_pack_edges", nv.ptr(self.col), nv.ptr(self.cdf), nv.ptr(self.guide), nv.i64(E),
-                        nv.ptr(self.packed), nv.stream())
+                nv.call("ps_pack_edges", nv.ptr(self.col), nv.ptr(self.cdf), nv.ptr(self.guide), E, nv.ptr(self.packed), nv.stream())
             # bucket records (one sector per later walk step).  Default: the 32-byte half records (four candidates' CDF entries as fp32
             # lower bounds + destinations) -- measured 5 % FASTER than the 64-byte records on SYN-25M too (0.406 against 0.431 ms per
             # two-layer launch, same box, alternating runs) at half the memory (1.6 GB instead of 3.2), and the only form that fits
@@ -78,12 +74,12 @@ class DeviceGraph:
                     form = "half" if E * 32 < (free * 3) // 5 else None
                 if form == "full":
                     self.buckets, self.bucket_bytes = torch.empty(E * 64, dtype=torch.uint8, device=dev), 64
-                    nv.call("ps_bucket_build", nv.ptr(self.rowptr), nv.ptr(self.col), nv.ptr(self.cdf), nv.ptr(self.guide),
-                            nv.i64(V), nv.i64(E), nv.ptr(self.buckets), nv.stream())
+                    nv.call("ps_bucket_build", nv.ptr(self.rowptr), nv.ptr(self.col), nv.ptr(self.cdf), nv.ptr(self.guide), V, E,
+                            nv.ptr(self.buckets), nv.stream())
                 elif form == "half":
                     self.buckets, self.bucket_bytes = torch.empty(E * 32, dtype=torch.uint8, device=dev), 32
-                    nv.call("ps_bucket_build_half", nv.ptr(self.rowptr), nv.ptr(self.col), nv.ptr(self.cdf), nv.ptr(self.guide),
-                            nv.i64(V), nv.i64(E), nv.ptr(self.buckets), nv.stream())
+                    nv.call("ps_bucket_build_half", nv.ptr(self.rowptr), nv.ptr(self.col), nv.ptr(self.cdf), nv.ptr(self.guide), V, E,
+                            nv.ptr(self.buckets), nv.stream())
             # destination records (8 bytes per edge, staged into LDS with a start row): a walk's second step without the gather of
             # its node record.  Built when the node records are NOT cache resident -- the default catalogue's 1.7 MB of them are L2
             # hits and the records bought nothing there (r03: 0.419 against 0.413 ms, tools/experiments/) -- i.e. for graphs of more
@@ -97,11 +93,9 @@ class DeviceGraph:
                 free = torch.cuda.mem_get_info(dev)[0]
                 if want is True or (V > self.DEST_INFO_MIN_NODES and E * 8 < free // 4):
                     self.dest_info = torch.empty(2 * E, dtype=torch.int32, device=dev)
-                    nv.call("ps_dest_info_build", nv.ptr(self.col), nv.ptr(self.nodeinfo), nv.i64(E), nv.i64(V),
-                            nv.ptr(self.dest_info), nv.stream())
+                    nv.call("ps_dest_info_build", nv.ptr(self.col), nv.ptr(self.nodeinfo), E, V, nv.ptr(self.dest_info), nv.stream())
             flags = torch.zeros(2, dtype=torch.int64, device=dev)
-            nv.call("ps_graph_stats", nv.ptr(self.rowptr), nv.ptr(self.col), nv.i64(E), nv.i64(V), nv.ptr(flags),
-                                      nv.stream())
+            nv.call("ps_graph_stats", nv.ptr(self.rowptr), nv.ptr(self.col), E, V, nv.ptr(flags), nv.stream())
             f = flags.tolist()
         self.has_reachable_sink = bool(f[0])
         self.max_degree = int(f[1])
@@ -161,28 +155,26 @@ class TargetCSR:
         self.rowptr = torch.empty(V + 1, dtype=torch.int64, device=dev)
         self.col = torch.empty(E, dtype=torch.int32, device=dev)
         order = torch.empty(E, dtype=torch.float64, device=dev)
-        L = nv.lib()
-        wsb = int(L.ps_csr_build_workspace_bytes(nv.i64(E), nv.i64(V)))
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        ws, wsb = nv.workspace("ps_csr_build_workspace_bytes", dev, E, V)
         # the "weight" channel carries the original edge number (exact in fp32 only below 2^24, so it is passed
         # through the fp64 output by building it in two halves)
         idx = torch.arange(E, device=dev)
         lo16 = (idx & 0xFFFF).to(torch.float32).contiguous()
         hi16 = (idx >> 16).to(torch.float32).contiguous()
         with torch.cuda.device(dev):
-            nv.call("ps_csr_build", nv.ptr(dst), nv.ptr(src), nv.ptr(lo16), nv.i64(E), nv.i64(V), nv.ptr(self.rowptr),
-                    nv.ptr(self.col), nv.ptr(order), nv.ptr(ws), nv.C.c_size_t(wsb), nv.stream())
+            nv.call("ps_csr_build", nv.ptr(dst), nv.ptr(src), nv.ptr(lo16), E, V, nv.ptr(self.rowptr), nv.ptr(self.col),
+                    nv.ptr(order), nv.ptr(ws), wsb, nv.stream())
             lo_sorted = order.clone()
-            nv.call("ps_csr_build", nv.ptr(dst), nv.ptr(src), nv.ptr(hi16), nv.i64(E), nv.i64(V), nv.ptr(self.rowptr),
-                    nv.ptr(self.col), nv.ptr(order), nv.ptr(ws), nv.C.c_size_t(wsb), nv.stream())
+            nv.call("ps_csr_build", nv.ptr(dst), nv.ptr(src), nv.ptr(hi16), E, V, nv.ptr(self.rowptr), nv.ptr(self.col),
+                    nv.ptr(order), nv.ptr(ws), wsb, nv.stream())
         self.perm = (order.to(torch.int64) << 16) | lo_sorted.to(torch.int64)
 
 
 def spmm_csr(tcsr, x, val=None):
     """out[r] = sum_e val[e] * x[col[e]] over row r of a TargetCSR (val in CSR slot order)."""
     x = x.contiguous()
-    out = torch.empty((tcsr.V, int(x.size(1))), dtype=torch.float32, device=x.device)
+    out = torch.empty((tcsr.V, x.size(1)), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        nv.call("ps_spmm_csr", nv.ptr(tcsr.rowptr), nv.ptr(tcsr.col), nv.ptr(val), nv.ptr(x), nv.i64(int(x.size(0))),
-                nv.i32(int(x.size(1))), nv.i64(tcsr.V), nv.i64(tcsr.E), nv.ptr(out), nv.stream())
+        nv.call("ps_spmm_csr", nv.ptr(tcsr.rowptr), nv.ptr(tcsr.col), nv.ptr(val), nv.ptr(x), x.size(0), x.size(1), tcsr.V, tcsr.E,
+                nv.ptr(out), nv.stream())
     return out

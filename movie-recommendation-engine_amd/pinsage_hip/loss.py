@@ -16,7 +16,6 @@ from torch.autograd.function import once_differentiable
 from . import native as nv
 
 SHARED, PER_QUERY, BATCH_HARD = nv.PS_LOSS_SHARED, nv.PS_LOSS_PER_QUERY, nv.PS_LOSS_BATCH_HARD
-f32 = nv.C.c_float
 
 
 def _fp32_cuda(name, t, dim):
@@ -48,8 +47,7 @@ def _best(Q, X, mode, exclude_diag, sim=None, idx=None):
     best = torch.empty(B, dtype=torch.int64, device=Q.device)
     flags = (nv.PS_HN_PER_QUERY if mode == PER_QUERY else 0) | (nv.PS_HN_EXCLUDE_DIAG if exclude_diag else 0)
     with torch.cuda.device(Q.device):
-        nv.call("ps_hardest_negative", nv.ptr(Q), nv.i64(B), nv.i32(D), nv.ptr(X), nv.i64(N), nv.i32(flags), nv.ptr(best),
-                nv.ptr(sim), nv.ptr(idx), nv.stream())
+        nv.call("ps_hardest_negative", nv.ptr(Q), B, D, nv.ptr(X), N, flags, nv.ptr(best), nv.ptr(sim), nv.ptr(idx), nv.stream())
     return best
 
 
@@ -89,8 +87,8 @@ class _MarginLoss(torch.autograd.Function):
         active = torch.empty(B, dtype=torch.uint8, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            nv.call("ps_margin_loss", nv.ptr(Q), nv.ptr(P), nv.i64(B), nv.i32(D), nv.ptr(best), f32(float(margin)),
-                    nv.ptr(row_loss), nv.ptr(idx), nv.ptr(active), nv.ptr(loss), nv.stream())
+            nv.call("ps_margin_loss", nv.ptr(Q), nv.ptr(P), B, D, nv.ptr(best), float(margin), nv.ptr(row_loss), nv.ptr(idx),
+                    nv.ptr(active), nv.ptr(loss), nv.stream())
         ctx.mode = mode
         ctx.save_for_backward(Q, P, X, idx, active)
         return loss
@@ -108,8 +106,8 @@ class _MarginLoss(torch.autograd.Function):
         dX = torch.empty_like(X) if need_x else None
         go = grad_out.to(device=Q.device, dtype=torch.float32).reshape(1).contiguous()
         with torch.cuda.device(Q.device):
-            nv.call("ps_margin_loss_bwd", nv.ptr(Q), nv.ptr(P), nv.ptr(X), nv.i64(B), nv.i64(N), nv.i32(D), nv.i32(mode),
-                    nv.ptr(idx), nv.ptr(active), nv.ptr(go), nv.ptr(dQ), nv.ptr(dP), nv.ptr(dX), nv.stream())
+            nv.call("ps_margin_loss_bwd", nv.ptr(Q), nv.ptr(P), nv.ptr(X), B, N, D, mode, nv.ptr(idx), nv.ptr(active), nv.ptr(go),
+                    nv.ptr(dQ), nv.ptr(dP), nv.ptr(dX), nv.stream())
         return dQ, dP, dX, None, None
 
 

@@ -33,17 +33,69 @@ class NativeError(RuntimeError):
     pass
 
 
-# every exported symbol of include/pinsage_hip.h (checked by tests/test_abi.py)
-SYMBOLS = [
-    "ps_abi_version", "ps_error_string", "ps_csr_build_workspace_bytes", "ps_csr_build", "ps_cdf_build",
-    "ps_guide_build", "ps_pack_edges", "ps_bucket_build", "ps_bucket_build_half", "ps_dest_info_build", "ps_graph_stats", "ps_walk_sample", "ps_walk_sample_layers", "ps_walk_paths", "ps_uniform_offsets", "ps_mt19937_window_shift", "ps_mt19937_workspace_bytes", "ps_mt19937_chunk_log2", "ps_mt19937_random_sample", "ps_mt19937_raw_stream",
-    "ps_importance_pool", "ps_permute_k", "ps_linear", "ps_gcn_layer_workspace_bytes", "ps_gcn_layer", "ps_lsh_encode", "ps_hamming_topk_workspace_bytes", "ps_hamming_topk",
-    "ps_lsh_planes_bytes", "ps_lsh_expand", "ps_hamming_topk_mfma_workspace_bytes", "ps_hamming_topk_mfma", "ps_hamming_topk_mfma_codes",
-    "ps_topk_merge", "ps_topk_merge_strided", "ps_dot_topk_workspace_bytes", "ps_dot_topk", "ps_row_dot", "ps_rank_count", "ps_l2_topk_workspace_bytes", "ps_l2_topk", "ps_ivf_topk_workspace_bytes", "ps_ivf_topk", "ps_spmm_csr",
-    "ps_cooc_planes_bytes", "ps_cooc_planes", "ps_cooc_pairs", "ps_cooc_pairs_sparse_workspace_bytes", "ps_cooc_pairs_sparse", "ps_cooc_keys",
-    "ps_cooc_emit",
-    "ps_hardest_negative", "ps_margin_loss", "ps_margin_loss_bwd",
-]
+# Every exported symbol of include/pinsage_hip.h as "<return> <parameters>", one letter per C type (tests/test_abi.py holds the
+# table to the header): p any pointer or ps_stream_t, q int64_t, i int, z size_t, Q uint64_t, I uint32_t, f float,
+# s const char *.  lib() turns each entry into restype / argtypes, so a call site passes plain Python values and a value of
+# the wrong kind, or a missing argument, is a ctypes.ArgumentError instead of a truncated word on the device.
+_CTYPES = {"p": C.c_void_p, "q": C.c_int64, "i": C.c_int, "z": C.c_size_t, "Q": C.c_uint64, "I": C.c_uint32, "f": C.c_float,
+           "s": C.c_char_p}
+PROTOTYPES = {
+    "ps_abi_version": "i",
+    "ps_error_string": "s i",
+    "ps_csr_build_workspace_bytes": "z qq",
+    "ps_csr_build": "i pppqqppppzp",
+    "ps_cdf_build": "i ppqpp",
+    "ps_guide_build": "i ppqppp",
+    "ps_pack_edges": "i pppqpp",
+    "ps_bucket_build": "i ppppqqpp",
+    "ps_bucket_build_half": "i ppppqqpp",
+    "ps_dest_info_build": "i ppqqpp",
+    "ps_graph_stats": "i ppqqpp",
+    "ps_walk_sample": "i pppqpqiiiippQIppppppppp",
+    "ps_walk_sample_layers": "i pppqpqiiiippqQIpppppipppp",
+    "ps_walk_paths": "i pppqpqiippQIipppp",
+    "ps_uniform_offsets": "i pqpqiippp",
+    "ps_mt19937_chunk_log2": "i",
+    "ps_mt19937_window_shift": "i",
+    "ps_mt19937_raw_stream": "i piqppppipipipipzp",
+    "ps_mt19937_workspace_bytes": "z qq",
+    "ps_mt19937_random_sample": "i piqqppppipipipzp",
+    "ps_importance_pool": "i pqippppqiqipp",
+    "ps_permute_k": "i pqiipp",
+    "ps_linear": "i pqipipipipiipp",
+    "ps_gcn_layer_workspace_bytes": "z qi",
+    "ps_gcn_layer": "i pqipipipqippppiqipiippzp",
+    "ps_lsh_encode": "i pqipipip",
+    "ps_hamming_topk_workspace_bytes": "z qqii",
+    "ps_hamming_topk": "i pqpqiiqpppzp",
+    "ps_lsh_planes_bytes": "z qi",
+    "ps_lsh_expand": "i pqipp",
+    "ps_hamming_topk_mfma_workspace_bytes": "z qqii",
+    "ps_hamming_topk_mfma": "i pqpqiiqpppzp",
+    "ps_hamming_topk_mfma_codes": "i pqpqiiqpppzp",
+    "ps_topk_merge": "i ppiqippp",
+    "ps_topk_merge_strided": "i pqpqiqippp",
+    "ps_dot_topk_workspace_bytes": "z qqii",
+    "ps_dot_topk": "i pqipqiipppzp",
+    "ps_row_dot": "i pqpqippqpp",
+    "ps_rank_count": "i pqiqpqpppp",
+    "ps_l2_topk_workspace_bytes": "z qqii",
+    "ps_l2_topk": "i pqipqippipppzp",
+    "ps_ivf_topk_workspace_bytes": "z qqiiiiq",
+    "ps_ivf_topk": "i pqipiqppqpiipppzp",
+    "ps_spmm_csr": "i ppppqiqqpp",
+    "ps_cooc_planes_bytes": "z qqi",
+    "ps_cooc_planes": "i pppqqqipzppp",
+    "ps_cooc_pairs": "i pqqiqpqpqppp",
+    "ps_cooc_pairs_sparse_workspace_bytes": "z qi",
+    "ps_cooc_pairs_sparse": "i pppppppqqqqqipqpppzp",
+    "ps_cooc_keys": "i pqqqppppppqpp",
+    "ps_cooc_emit": "i ppqppp",
+    "ps_hardest_negative": "i pqipqipppp",
+    "ps_margin_loss": "i ppqipfppppp",
+    "ps_margin_loss_bwd": "i pppqqiippppppp",
+}
+SYMBOLS = list(PROTOTYPES)
 
 
 def have_lib() -> bool:
@@ -57,14 +109,15 @@ def lib():
             raise LibraryMissing(
                 f"{SO_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950).  There is no CPU fallback for the PinSage hot path.")
-        _lib = C.CDLL(SO_PATH)
-        _lib.ps_error_string.restype = C.c_char_p
-        for name in ("ps_csr_build_workspace_bytes", "ps_hamming_topk_workspace_bytes", "ps_dot_topk_workspace_bytes",
-                     "ps_l2_topk_workspace_bytes", "ps_ivf_topk_workspace_bytes", "ps_mt19937_workspace_bytes", "ps_lsh_planes_bytes",
-                     "ps_hamming_topk_mfma_workspace_bytes", "ps_gcn_layer_workspace_bytes", "ps_cooc_planes_bytes",
-                     "ps_cooc_pairs_sparse_workspace_bytes"):
-            if hasattr(_lib, name):
-                getattr(_lib, name).restype = C.c_size_t
+        L = C.CDLL(SO_PATH)
+        for name, code in PROTOTYPES.items():
+            try:
+                fn = getattr(L, name)
+            except AttributeError:
+                raise NativeError(f"{SO_PATH} does not export {name} (include/pinsage_hip.h): rebuild it") from None
+            ret, _, params = code.partition(" ")
+            fn.restype, fn.argtypes = _CTYPES[ret], [_CTYPES[c] for c in params]
+        _lib = L
     return _lib
 
 
@@ -114,15 +167,23 @@ def call(name, *args):
     check(rc, name)
 
 
-def ptr(t):
-    """Device pointer of a contiguous CUDA tensor (None -> NULL)."""
+def ptr(t, contiguous=True):
+    """Device pointer of a contiguous CUDA tensor (None -> NULL); contiguous=False takes a strided view as it is (a weight
+    matrix passed with its leading dimension)."""
     if t is None:
         return C.c_void_p(0)
     if not t.is_cuda:
         raise NativeError("libpinsage_hip takes device (HBM) pointers; got a CPU tensor")
-    if not t.is_contiguous():
+    if contiguous and not t.is_contiguous():
         raise NativeError("tensor must be contiguous")
     return C.c_void_p(t.data_ptr())
+
+
+def workspace(bytes_fn, device, *dims):
+    """(uint8 scratch tensor on `device`, its size in bytes) as the library's `bytes_fn` sizes it for `dims`; (None, 0) when it
+    answers 0 -- whether that means "nothing needed" or "shape not served" is the caller's to know."""
+    nbytes = getattr(lib(), bytes_fn)(*dims)
+    return (torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None), nbytes
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -145,6 +206,7 @@ def require_gpu():
     return torch.device("cuda", torch.cuda.current_device())
 
 
+# the scalar types of the table by name, for callers of exports outside it (ps_debug_*: tools/) and for tests
 i64 = C.c_int64
 i32 = C.c_int
 u64 = C.c_uint64

@@ -160,9 +160,9 @@ def sink_walk_offsets(graph, starts, W, L, uniforms):
         off = (torch.cumsum(steps, 0) - steps).contiguous()
         if B * W == 0:
             break
-        nv.call("ps_walk_paths", nv.ptr(graph.rowptr), nv.ptr(graph.col), nv.ptr(graph.cdf), nv.i64(graph.V),
-                nv.ptr(walks), nv.i64(B * W), nv.i32(L), nv.i32(nv.PS_RNG_STREAM), nv.ptr(uniforms), nv.ptr(off),
-                nv.u64(0), nv.u32(0), nv.i32(0), nv.ptr(graph.nodeinfo), nv.ptr(graph.guide), nv.ptr(paths), nv.stream())
+        nv.call("ps_walk_paths", nv.ptr(graph.rowptr), nv.ptr(graph.col), nv.ptr(graph.cdf), graph.V, nv.ptr(walks), B * W, L,
+                nv.PS_RNG_STREAM, nv.ptr(uniforms), nv.ptr(off), 0, 0, 0, nv.ptr(graph.nodeinfo), nv.ptr(graph.guide),
+                nv.ptr(paths), nv.stream())
         took = (paths >= 0).sum(dim=1)
         if torch.equal(took, steps):
             return off, int(steps.sum().item())
@@ -202,7 +202,6 @@ def walk_sample(graph, nodes, T, W=100, L=2, rng="numpy", seed=0, call=0, unifor
     ids = torch.empty((B, T), dtype=torch.int32, device=dev)
     counts = torch.empty((B, T), dtype=torch.int32, device=dev)
     nvalid = torch.empty(B, dtype=torch.int32, device=dev)
-    L_ = nv.lib()
     with torch.cuda.device(dev):
         if rng == "numpy" and graph.has_reachable_sink:
             # data-dependent RNG consumption (utils/random_walk.py:65-69): per-walk stream positions by fixpoint
@@ -220,13 +219,13 @@ def walk_sample(graph, nodes, T, W=100, L=2, rng="numpy", seed=0, call=0, unifor
                 all_nodes, lo = stream_nodes
                 all_nodes = _nodes_tensor(all_nodes, dev, graph.V)
                 uoff_all = torch.empty(all_nodes.numel(), dtype=torch.int64, device=dev)
-                nv.call("ps_uniform_offsets", nv.ptr(graph.rowptr), nv.i64(graph.V), nv.ptr(all_nodes),
-                        nv.i64(all_nodes.numel()), nv.i32(W), nv.i32(L), nv.ptr(uoff_all), nv.ptr(total), nv.stream())
+                nv.call("ps_uniform_offsets", nv.ptr(graph.rowptr), graph.V, nv.ptr(all_nodes), all_nodes.numel(), W, L,
+                        nv.ptr(uoff_all), nv.ptr(total), nv.stream())
                 uoff = uoff_all[lo:lo + B].contiguous()
             else:
                 uoff = torch.empty(B, dtype=torch.int64, device=dev)
-                nv.call("ps_uniform_offsets", nv.ptr(graph.rowptr), nv.i64(graph.V), nv.ptr(starts), nv.i64(B),
-                        nv.i32(W), nv.i32(L), nv.ptr(uoff), nv.ptr(total), nv.stream())
+                nv.call("ps_uniform_offsets", nv.ptr(graph.rowptr), graph.V, nv.ptr(starts), B, W, L, nv.ptr(uoff), nv.ptr(total),
+                        nv.stream())
             if uniforms is None:
                 n = int(total.item())
                 uniforms = draw_numpy_uniforms(n, dev)
@@ -235,16 +234,14 @@ def walk_sample(graph, nodes, T, W=100, L=2, rng="numpy", seed=0, call=0, unifor
             uoff, uniforms, mode = None, None, nv.PS_RNG_PHILOX
         else:
             raise ValueError("rng must be 'numpy' or 'philox'")
-        nv.call("ps_walk_sample", nv.ptr(graph.rowptr), nv.ptr(graph.col), nv.ptr(graph.cdf), nv.i64(graph.V),
-                                   nv.ptr(starts), nv.i64(B), nv.i32(W), nv.i32(L), nv.i32(T),
-                                   nv.i32(mode | (graph.walk_flags if (use_guide and use_buckets) else 0)),
-                                   nv.ptr(uniforms), nv.ptr(uoff), nv.u64(seed & (2 ** 64 - 1)), nv.u32(call),
-                                   nv.ptr(graph.nodeinfo) if use_guide else nv.ptr(None),
-                                   nv.ptr(graph.guide) if use_guide else nv.ptr(None),
-                                   nv.ptr(graph.packed) if (use_guide and use_packed) else nv.ptr(None),
-                                   nv.ptr(getattr(graph, "buckets", None)) if (use_guide and use_buckets) else nv.ptr(None),
-                                   nv.ptr(getattr(graph, "dest_info", None)) if (use_guide and use_packed and use_dest) else nv.ptr(None),
-                                   nv.ptr(ids), nv.ptr(counts), nv.ptr(nvalid), nv.stream())
+        packed = use_guide and use_packed
+        nv.call("ps_walk_sample", nv.ptr(graph.rowptr), nv.ptr(graph.col), nv.ptr(graph.cdf), graph.V, nv.ptr(starts), B, W, L, T,
+                mode | (graph.walk_flags if (use_guide and use_buckets) else 0), nv.ptr(uniforms), nv.ptr(uoff),
+                seed & (2 ** 64 - 1), call, nv.ptr(graph.nodeinfo if use_guide else None), nv.ptr(graph.guide if use_guide else None),
+                nv.ptr(graph.packed if packed else None),
+                nv.ptr(getattr(graph, "buckets", None) if (use_guide and use_buckets) else None),
+                nv.ptr(getattr(graph, "dest_info", None) if (packed and use_dest) else None),
+                nv.ptr(ids), nv.ptr(counts), nv.ptr(nvalid), nv.stream())
     return NeighborBatch(ids, counts, nvalid)
 
 
@@ -295,8 +292,8 @@ def walk_sample_layers(graph, nodes, T, layers, W=100, L=2, rng="numpy", seed=0,
                          if isinstance(src, range) else _nodes_tensor(src, dev, graph.V))
                 total = torch.empty(1, dtype=torch.int64, device=dev)
                 uoff_all = torch.empty(all_t.numel(), dtype=torch.int64, device=dev)
-                nv.call("ps_uniform_offsets", nv.ptr(graph.rowptr), nv.i64(graph.V), nv.ptr(all_t),
-                        nv.i64(all_t.numel()), nv.i32(W), nv.i32(L), nv.ptr(uoff_all), nv.ptr(total), nv.stream())
+                nv.call("ps_uniform_offsets", nv.ptr(graph.rowptr), graph.V, nv.ptr(all_t), all_t.numel(), W, L, nv.ptr(uoff_all),
+                        nv.ptr(total), nv.stream())
                 stride = int(total.item())
                 if key is not None:
                     cache[key] = (uoff_all, stride)
@@ -330,12 +327,11 @@ def walk_sample_layers(graph, nodes, T, layers, W=100, L=2, rng="numpy", seed=0,
             u = uniforms
             if uniforms is not None and r0:
                 u = uniforms[2 * r0 * stride:] if mode == nv.PS_RNG_STREAM_RAW else uniforms[r0 * stride:]
-            nv.call("ps_walk_sample_layers", nv.ptr(graph.rowptr), nv.ptr(graph.col), nv.ptr(graph.cdf), nv.i64(graph.V),
-                    nv.ptr(starts), nv.i64(B), nv.i32(W), nv.i32(L), nv.i32(T), nv.i32(mode | graph.walk_flags), nv.ptr(u), nv.ptr(uoff),
-                    nv.i64(stride), nv.u64(seed & (2 ** 64 - 1)), nv.u32(call + r0), nv.ptr(graph.nodeinfo), nv.ptr(graph.guide),
-                    nv.ptr(graph.packed), nv.ptr(getattr(graph, "buckets", None)), nv.ptr(getattr(graph, "dest_info", None)),
-                    nv.i32(n), nv.ptr(ids[r0:r0 + n]),
-                    nv.ptr(counts[r0:r0 + n]), nv.ptr(nvalid[r0:r0 + n]), nv.stream())
+            nv.call("ps_walk_sample_layers", nv.ptr(graph.rowptr), nv.ptr(graph.col), nv.ptr(graph.cdf), graph.V, nv.ptr(starts), B,
+                    W, L, T, mode | graph.walk_flags, nv.ptr(u), nv.ptr(uoff), stride, seed & (2 ** 64 - 1), call + r0,
+                    nv.ptr(graph.nodeinfo), nv.ptr(graph.guide), nv.ptr(graph.packed), nv.ptr(getattr(graph, "buckets", None)),
+                    nv.ptr(getattr(graph, "dest_info", None)), n, nv.ptr(ids[r0:r0 + n]), nv.ptr(counts[r0:r0 + n]),
+                    nv.ptr(nvalid[r0:r0 + n]), nv.stream())
     return [NeighborBatch(ids[r], counts[r], nvalid[r]) for r in range(layers)]
 
 
@@ -345,7 +341,6 @@ def walk_paths(graph, starts, L, rng="numpy", seed=0, call=0, walk_mod=0):
     st = _nodes_tensor(starts, dev, graph.V)
     B = int(st.numel())
     paths = torch.empty((B, L), dtype=torch.int32, device=dev)
-    L_ = nv.lib()
     with torch.cuda.device(dev):
         if rng == "numpy" and graph.has_reachable_sink:
             uniforms, uoff = _sink_stream(graph, st, 1, L)       # one walk per start node: W = 1
@@ -353,16 +348,14 @@ def walk_paths(graph, starts, L, rng="numpy", seed=0, call=0, walk_mod=0):
         elif rng == "numpy":
             uoff = torch.empty(B, dtype=torch.int64, device=dev)
             total = torch.empty(1, dtype=torch.int64, device=dev)
-            nv.call("ps_uniform_offsets", nv.ptr(graph.rowptr), nv.i64(graph.V), nv.ptr(st), nv.i64(B), nv.i32(1),
-                                           nv.i32(L), nv.ptr(uoff), nv.ptr(total), nv.stream())
+            nv.call("ps_uniform_offsets", nv.ptr(graph.rowptr), graph.V, nv.ptr(st), B, 1, L, nv.ptr(uoff), nv.ptr(total), nv.stream())
             uniforms = draw_numpy_uniforms(int(total.item()), dev)
             mode = nv.PS_RNG_STREAM
         else:
             uoff, uniforms, mode = None, None, nv.PS_RNG_PHILOX
-        nv.call("ps_walk_paths", nv.ptr(graph.rowptr), nv.ptr(graph.col), nv.ptr(graph.cdf), nv.i64(graph.V),
-                                  nv.ptr(st), nv.i64(B), nv.i32(L), nv.i32(mode), nv.ptr(uniforms), nv.ptr(uoff),
-                                  nv.u64(seed & (2 ** 64 - 1)), nv.u32(call), nv.i32(walk_mod), nv.ptr(graph.nodeinfo),
-                                  nv.ptr(graph.guide), nv.ptr(paths), nv.stream())
+        nv.call("ps_walk_paths", nv.ptr(graph.rowptr), nv.ptr(graph.col), nv.ptr(graph.cdf), graph.V, nv.ptr(st), B, L, mode,
+                nv.ptr(uniforms), nv.ptr(uoff), seed & (2 ** 64 - 1), call, walk_mod, nv.ptr(graph.nodeinfo), nv.ptr(graph.guide),
+                nv.ptr(paths), nv.stream())
     return paths
 
 
@@ -374,15 +367,14 @@ def importance_pool(x, batch: NeighborBatch = None, ids=None, counts=None, wts=N
     x = x.contiguous()
     if x.dtype != torch.float32:
         raise TypeError("importance_pool expects fp32 features")
-    B, T = int(ids.size(0)), int(ids.size(1))
-    N, H = int(x.size(0)), int(x.size(1))
+    B, T = ids.size(0), ids.size(1)
+    N, H = x.size(0), x.size(1)
     out = torch.empty((B, H), dtype=torch.float32, device=x.device)
     if max_idx is None:
         max_idx = N - 1
     with torch.cuda.device(x.device):
-        nv.call("ps_importance_pool", nv.ptr(x), nv.i64(N), nv.i32(H), nv.ptr(ids), nv.ptr(counts), nv.ptr(wts),
-                                             nv.ptr(nvalid), nv.i64(B), nv.i32(T), nv.i64(max_idx), nv.i32(int(renorm)),
-                                             nv.ptr(out), nv.stream())
+        nv.call("ps_importance_pool", nv.ptr(x), N, H, nv.ptr(ids), nv.ptr(counts), nv.ptr(wts), nv.ptr(nvalid), B, T, max_idx,
+                int(renorm), nv.ptr(out), nv.stream())
     return out
 
 
