@@ -233,3 +233,58 @@ def dot_topk(E, qidx, k, exclude_self=True, threads=1):
     _check(lib().orc_dot_topk(_p(E), C.c_int64(E.shape[0]), C.c_int(E.shape[1]), _p(qidx), C.c_int64(qidx.shape[0]),
                               C.c_int(k), C.c_int(int(exclude_self)), _p(vals), _p(ids), C.c_int(threads)), "orc_dot_topk")
     return vals, ids
+
+
+def hardest_negative(Q, X, per_query=False, exclude_diag=False, threads=1):
+    """orc_hardest_negative -> (sim fp32 [B], idx int64 [B]): per row of Q the largest fmaf-chain similarity and the smallest index
+    that attains it.  X [N, D] shared (exclude_diag leaves j == b out; -inf / -1 for a row without a candidate) or [B, N, D]."""
+    Q = np.ascontiguousarray(Q, dtype=np.float32)
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    B, D = Q.shape
+    if (X.ndim != 3 or X.shape[0] != B) if per_query else X.ndim != 2:
+        raise ValueError("shape mismatch")
+    N = X.shape[1] if per_query else X.shape[0]
+    if X.shape[-1] != D:
+        raise ValueError("shape mismatch")
+    sim = np.empty(B, dtype=np.float32)
+    idx = np.empty(B, dtype=np.int64)
+    _check(lib().orc_hardest_negative(_p(Q), C.c_int64(B), C.c_int(D), _p(X), C.c_int64(N), C.c_int(int(per_query)),
+                                      C.c_int(int(exclude_diag)), _p(sim), _p(idx), C.c_int(threads)), "orc_hardest_negative")
+    return sim, idx
+
+
+def margin_loss(Q, P, sim, margin):
+    """orc_margin_loss -> (row_loss fp32 [B], active uint8 [B], loss fp32 scalar): relu((margin + sim_b) - Q_b . P_b), the rows
+    that pass a gradient, and the mean by ps_margin_loss's reduction of fixed shape."""
+    Q = np.ascontiguousarray(Q, dtype=np.float32)
+    P = np.ascontiguousarray(P, dtype=np.float32)
+    sim = np.ascontiguousarray(sim, dtype=np.float32)
+    B, D = Q.shape
+    if P.shape != (B, D) or sim.shape != (B,):
+        raise ValueError("shape mismatch")
+    row_loss = np.empty(B, dtype=np.float32)
+    active = np.empty(B, dtype=np.uint8)
+    loss = np.empty(1, dtype=np.float32)
+    _check(lib().orc_margin_loss(_p(Q), _p(P), C.c_int64(B), C.c_int(D), _p(sim), C.c_float(float(margin)), _p(row_loss),
+                                 _p(active), _p(loss)), "orc_margin_loss")
+    return row_loss, active, loss[0]
+
+
+def margin_loss_bwd(Q, P, X, mode, idx, active, go, want=("dQ", "dP", "dX")):
+    """orc_margin_loss_bwd -> {name: fp32 array} for the names in `want` that the mode has (0 shared: X [N, D]; 1 per-query:
+    X [B, N, D]; 2 batch-hard: X None, no dX): the header's closed form, one rounded fp32 operation per statement."""
+    Q = np.ascontiguousarray(Q, dtype=np.float32)
+    P = np.ascontiguousarray(P, dtype=np.float32)
+    X = None if X is None else np.ascontiguousarray(X, dtype=np.float32)
+    idx = np.ascontiguousarray(idx, dtype=np.int64)
+    active = np.ascontiguousarray(active, dtype=np.uint8)
+    B, D = Q.shape
+    N = B if mode == 2 else X.shape[1] if mode == 1 else X.shape[0]
+    if P.shape != (B, D) or idx.shape != (B,) or active.shape != (B,) or (mode != 2 and X.shape[-1] != D):
+        raise ValueError("shape mismatch")
+    out = {"dQ": np.empty_like(Q) if "dQ" in want else None, "dP": np.empty_like(P) if "dP" in want else None,
+           "dX": np.empty_like(X) if "dX" in want and mode != 2 else None}
+    _check(lib().orc_margin_loss_bwd(_p(Q), _p(P), _p(X), C.c_int64(B), C.c_int64(N), C.c_int(D), C.c_int(mode), _p(idx),
+                                     _p(active), C.c_float(float(go)), _p(out["dQ"]), _p(out["dP"]), _p(out["dX"])),
+           "orc_margin_loss_bwd")
+    return {k: v for k, v in out.items() if v is not None}

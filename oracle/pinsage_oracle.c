@@ -461,6 +461,124 @@ int orc_dot_topk(const float *E, int64_t N, int D, const int64_t *qidx, int64_t 
     return ORC_OK;
 }
 
+/* ---------- the ranking losses (include/pinsage_hip.h: ps_hardest_negative, ps_margin_loss, ps_margin_loss_bwd), the header's
+ * formulas with ONE rounded fp32 operation per statement, in the header's order.  No NaN handling: a test keeps its inputs finite. */
+
+/* acc = fmaf(q[k], x[k], acc), k ascending from +0.0 (orc_linear's chain; from +0.0 it never ends in -0.0) */
+static float orc_chain(const float *q, const float *x, int D) {
+    float acc = 0.f;
+    for (int k = 0; k < D; k++) acc = fmaf(q[k], x[k], acc);
+    return acc;
+}
+
+/* sim[b] = max_j Q_b . X_j, idx[b] = the smallest j that attains it; -inf / -1 for a row without a candidate.
+ * per_query: X [B, N, D], row b sees X[b]; else X [N, D], exclude_diag leaves j == b out. */
+int orc_hardest_negative(const float *Q, int64_t B, int D, const float *X, int64_t N, int per_query, int exclude_diag,
+                         float *sim, int64_t *idx, int threads) {
+    if (B < 0 || N < 0 || D <= 0 || (per_query && exclude_diag)) return ORC_EINVAL;
+#ifdef _OPENMP
+#pragma omp parallel for schedule(static) num_threads(threads > 0 ? threads : 1)
+#endif
+    for (int64_t b = 0; b < B; b++) {
+        const float *q = Q + b * D;
+        const float *x = per_query ? X + b * N * D : X;
+        float best = -INFINITY;
+        int64_t at = -1;
+        for (int64_t j = 0; j < N; j++) {
+            if (exclude_diag && j == b) continue;
+            const float s = orc_chain(q, x + j * D, D);
+            if (at < 0 || s > best) { best = s; at = j; }
+        }
+        sim[b] = best;
+        idx[b] = at;
+    }
+    return ORC_OK;
+}
+
+#define ORC_MEAN_THREADS 1024
+/* mean_kernel restated: 1024 strided partial sums, the tree s[i] += s[i + w] for w = 512 .. 1, then s[0] / (float)B */
+static float orc_fixed_mean(const float *v, int64_t B) {
+    float s[ORC_MEAN_THREADS];
+    for (int tid = 0; tid < ORC_MEAN_THREADS; tid++) {
+        float t = 0.f;
+        for (int64_t b = tid; b < B; b += ORC_MEAN_THREADS) t += v[b];
+        s[tid] = t;
+    }
+    for (int w = ORC_MEAN_THREADS / 2; w > 0; w >>= 1)
+        for (int i = 0; i < w; i++) s[i] += s[i + w];
+    return s[0] / (float)B;
+}
+
+int orc_margin_loss(const float *Q, const float *P, int64_t B, int D, const float *sim, float margin, float *row_loss,
+                    uint8_t *active, float *loss) {
+    if (B <= 0 || D <= 0) return ORC_EINVAL;
+    for (int64_t b = 0; b < B; b++) {
+        const float pos = orc_chain(Q + b * D, P + b * D, D);
+        const float ms = margin + sim[b];
+        const float l = ms - pos;
+        row_loss[b] = l <= 0.f ? 0.f : l;
+        active[b] = l <= 0.f ? 0 : 1;
+    }
+    loss[0] = orc_fixed_mean(row_loss, B);
+    return ORC_OK;
+}
+
+/* mode 0 shared (X [N, D]), 1 per-query (X [B, N, D]), 2 batch-hard (X ignored: the candidates are P, N == B, dX NULL).
+ * dQ / dP / dX: NULL = not computed. */
+int orc_margin_loss_bwd(const float *Q, const float *P, const float *X, int64_t B, int64_t N, int D, int mode,
+                        const int64_t *idx, const uint8_t *active, float go, float *dQ, float *dP, float *dX) {
+    if (B <= 0 || N < 0 || D <= 0 || mode < 0 || mode > 2) return ORC_EINVAL;
+    if (mode == 2 && (N != B || dX)) return ORC_EINVAL;
+    const float g = go / (float)B;
+    const float *cand = mode == 2 ? P : X;
+    /* the row part */
+    for (int64_t b = 0; b < B; b++) {
+        const int64_t a = idx[b];
+        const int hit = a >= 0 && a < N;
+        const float gb = (active[b] && hit) ? g : 0.f;
+        const float ng = -gb;
+        const float *q = Q + b * D, *p = P + b * D;
+        if (dQ) {
+            const float *xa = hit ? cand + (mode == 1 ? b * N + a : a) * D : NULL;
+            for (int k = 0; k < D; k++) {
+                float t = 0.f;
+                if (hit) t = gb * xa[k];
+                const float u = ng * p[k];
+                dQ[b * D + k] = t + u;
+            }
+        }
+        if (dP && mode != 2)
+            for (int k = 0; k < D; k++) dP[b * D + k] = ng * q[k];
+        if (dX && mode == 1)
+            for (int64_t n = 0; n < N; n++)
+                for (int k = 0; k < D; k++) dX[(b * N + n) * D + k] = n == a ? gb * q[k] : 0.f;
+    }
+    /* the scatter part: acc = acc + g * q_b[k] over the active rows with idx[b] == j, b ascending from +0.0 */
+    float *out = mode == 2 ? dP : mode == 0 ? dX : NULL;
+    if (out && N > 0) {
+        for (int64_t i = 0; i < N * D; i++) out[i] = 0.f;
+        for (int64_t b = 0; b < B; b++) {
+            const int64_t j = idx[b];
+            if (!active[b] || j < 0 || j >= N) continue;
+            for (int k = 0; k < D; k++) {
+                const float t = g * Q[b * D + k];
+                out[j * D + k] = out[j * D + k] + t;
+            }
+        }
+        if (mode == 2)
+            for (int64_t j = 0; j < N; j++) {
+                const int64_t a = idx[j];
+                const float gj = (active[j] && a >= 0 && a < N) ? g : 0.f;
+                const float ng = -gj;
+                for (int k = 0; k < D; k++) {
+                    const float u = ng * Q[j * D + k];
+                    out[j * D + k] = u + out[j * D + k];
+                }
+            }
+    }
+    return ORC_OK;
+}
+
 int orc_max_threads(void) {
 #ifdef _OPENMP
     return omp_get_max_threads();

@@ -154,3 +154,42 @@ def test_hamming_references_agree(cs, N, nq, k, kind):
         assert np.array_equal(rd[:, :kk].astype(np.int32), do[:, :kk])
     lead = (list(range(N)) if kind == "same" else pos)[:k]
     assert ref[1][0, :len(lead)].tolist() == lead and not ref[0][0, :len(lead)].any()
+
+
+def test_ranking_losses_by_hand():
+    """B = 3, N = 2, D = 2, margin 1/2, grad_out 3/2 (g = 1/2): every number is exact and small enough to check on paper.  Signs of
+    zeros are part of the contract: an inactive row's -g p is -0.0 and t + (-0.0) is +0.0."""
+    f = np.float32
+    bits = lambda a: np.ascontiguousarray(a, dtype=f).view(np.int32).tolist()      # noqa: E731
+    Q = np.array([[1, 2], [0.5, -1], [2, 0]], dtype=f)
+    P = np.array([[1, 1], [2, 0.5], [-1, 3]], dtype=f)
+    X = np.array([[1, 0], [0, 1]], dtype=f)
+    # shared candidates: similarities [[1, 2], [.5, -1], [2, 0]]; positives 3, .5, -2; l = -.5 (inactive), .5, 4.5
+    sim, idx = co.hardest_negative(Q, X)
+    assert sim.tolist() == [2.0, 0.5, 2.0] and idx.tolist() == [1, 0, 0]
+    row_loss, active, loss = co.margin_loss(Q, P, sim, 0.5)
+    assert row_loss.tolist() == [0.0, 0.5, 4.5] and active.tolist() == [0, 1, 1] and loss == f(5.0) / f(3.0)
+    g = co.margin_loss_bwd(Q, P, X, 0, idx, active, 1.5)
+    assert bits(g["dQ"]) == bits([[0.0, 0.0], [-0.5, -0.25], [1.0, -1.5]])         # row 1: .5 (1, 0) - .5 (2, .5)
+    assert bits(g["dP"]) == bits([[-0.0, -0.0], [-0.25, 0.5], [-1.0, -0.0]])
+    assert bits(g["dX"]) == bits([[1.25, -0.5], [0.0, 0.0]])                       # .5 Q_1 + .5 Q_2; row 0 is inactive
+    assert set(co.margin_loss_bwd(Q, P, X, 0, idx, active, 1.5, want=("dX",))) == {"dX"}
+    # per-query candidates, every row with the same two: the same pairs, dX [3, 2, 2] with the hit filled in
+    X3 = np.ascontiguousarray(np.broadcast_to(X, (3, 2, 2)))
+    sim3, idx3 = co.hardest_negative(Q, X3, per_query=True)
+    assert bits(sim3) == bits(sim) and idx3.tolist() == idx.tolist()
+    g3 = co.margin_loss_bwd(Q, P, X3, 1, idx, active, 1.5)
+    assert bits(g3["dQ"]) == bits(g["dQ"]) and bits(g3["dP"]) == bits(g["dP"])
+    assert bits(g3["dX"]) == bits([[[0, 0], [0, 0]], [[0.25, -0.5], [0, 0]], [[1.0, 0.0], [0, 0]]])
+    # batch-hard: Q P^T = [[3, 3, 5], [-.5, .5, -3.5], [2, 4, -2]] without its diagonal; l = 2.5, -.5 (inactive), 6.5
+    simh, idxh = co.hardest_negative(Q, P, exclude_diag=True)
+    assert simh.tolist() == [5.0, -0.5, 4.0] and idxh.tolist() == [2, 0, 1]
+    row_loss, active, loss = co.margin_loss(Q, P, simh, 0.5)
+    assert row_loss.tolist() == [2.5, 0.0, 6.5] and active.tolist() == [1, 0, 1] and loss == f(3.0)
+    gh = co.margin_loss_bwd(Q, P, None, 2, idxh, active, 1.5)
+    assert set(gh) == {"dQ", "dP"}
+    assert bits(gh["dQ"]) == bits([[-1.0, 1.0], [0.0, 0.0], [1.5, -1.25]])         # .5 P_2 - .5 P_0;  0;  .5 P_1 - .5 P_2
+    assert bits(gh["dP"]) == bits([[-0.5, -1.0], [1.0, 0.0], [-0.5, 1.0]])         # -g_j Q_j + .5 Q_b over active b with a_b = j
+    # a row without a candidate
+    s1, i1 = co.hardest_negative(Q[:1], P[:1], exclude_diag=True)
+    assert s1[0] == -np.inf and i1[0] == -1

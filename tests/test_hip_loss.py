@@ -21,10 +21,14 @@ ps_margin_loss_bwd).
 import ctypes
 import inspect
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from loss_cases import _closed_form, _closed_form_magnitude  # noqa: E402  (the fp64 closed form: shared with tests/test_loss_cases.py)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_golden_loss.npz")
@@ -69,44 +73,6 @@ def _run_form(ml, form, Q, P, X, hidx, dev, margin, scale=None):
     (loss if scale is None else loss * scale).backward()
     grads = tuple(None if v is None else v.grad.detach().cpu().numpy() for v in (q, p, x))
     return float(loss.detach()), grads
-
-
-def _closed_form(Q, P, X, idx, active, form, go=1.0):
-    """the gradient of include/pinsage_hip.h in float64; X as the form takes it ([N, D], [B, H, D] or [B, D])"""
-    Q, P = Q.astype(np.float64), P.astype(np.float64)
-    B = Q.shape[0]
-    rows = np.arange(B)
-    g = np.where(active, go / B, 0.0)[:, None]
-    if form == "bh":
-        dP = -g * Q
-        np.add.at(dP, idx, g * Q)
-        return g * P[idx] + (-g * P), dP, None
-    X = X.astype(np.float64)
-    dX = np.zeros_like(X)
-    if form == "shared":
-        np.add.at(dX, idx, g * Q)
-        return g * X[idx] + (-g * P), -g * Q, dX
-    if form == "twod":
-        dX[:] = g * Q
-        return g * X + (-g * P), -g * Q, dX
-    dX[rows, idx] = g * Q
-    return g * X[rows, idx] + (-g * P), -g * Q, dX
-
-
-def _closed_form_magnitude(Q, P, X, idx, active, form, go=1.0):
-    """per gradient entry (sum of the magnitudes of its terms, number of terms): the closed form over absolute values"""
-    aQ, aP = np.abs(Q), np.abs(P)
-    ones = np.ones_like(Q)
-    if form == "bh":                                  # dQ = g p_a - g p, dP = -g q + sum: every term with a plus sign
-        g, a = np.where(active, go / Q.shape[0], 0.0)[:, None], active[:, None] * ones
-        mP, cP = g * aQ, a.copy()
-        np.add.at(mP, idx, g * aQ)
-        np.add.at(cP, idx, a)
-        return {"dQ": (g * (aP[idx] + aP), 2 * a), "dP": (mP, cP)}
-    aX = np.abs(X)
-    mags = _closed_form(aQ, -aP, aX, idx, active, form, go)                   # -(-g |p|): every term enters with a plus sign
-    cnts = _closed_form(ones, -ones, np.ones_like(X), idx, active, form, float(Q.shape[0]))
-    return {k: (np.abs(m), np.abs(c)) for k, m, c in zip(("dQ", "dP", "dX"), mags, cnts) if m is not None}
 
 
 def _form_input(form, X, hidx):
