@@ -40,20 +40,6 @@ __device__ __forceinline__ float key_value(uint32_t kk) {
 // with 64 private thresholds some lane was inserting at nearly every element, and the wave sat in a divergent LDS insertion
 // loop for the whole row (1.06 ms per 4 546 x 59 047 slab).
 constexpr int SELQ = 256;
-__device__ __forceinline__ uint64_t wave_min_key(uint64_t v) {
-#define PS_STEP(ctrl, rows)                                                                                     \
-    {                                                                                                           \
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)(uint32_t)v, ctrl, rows, 0xf, false); \
-        const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)(uint32_t)(v >> 32), ctrl, rows, 0xf, false); \
-        const uint64_t o = ((uint64_t)hi << 32) | lo;                                                           \
-        v = o < v ? o : v;                                                                                      \
-    }
-    PS_STEP(0xB1, 0xf) PS_STEP(0x4E, 0xf) PS_STEP(0x141, 0xf) PS_STEP(0x140, 0xf) PS_STEP(0x142, 0xa) PS_STEP(0x143, 0xc)
-#undef PS_STEP
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63);
-    return ((uint64_t)hi << 32) | lo;
-}
 struct WaveSelect {
     uint64_t *q;          // LDS, SELQ keys of this wave
     int lane, kk, cnt;    // cnt: wave-uniform
@@ -73,7 +59,7 @@ struct WaveSelect {
             uint64_t m = r[0];
 #pragma unroll
             for (int u = 1; u < SELQ / 64; ++u) m = r[u] < m ? r[u] : m;
-            const uint64_t w = wave_min_key(m);
+            const uint64_t w = ps_wave_min_u64(m);
             if (w == EMPTY_KEY) break;
 #pragma unroll
             for (int u = 0; u < SELQ / 64; ++u) if (r[u] == w) r[u] = EMPTY_KEY;      // keys are unique

@@ -89,7 +89,16 @@ constexpr int WAVES = 8;
 constexpr int PAD_TILES = 4;               // plane tables are padded to whole ring entries (2 or 4 item tiles of 32 codes)
 constexpr float NO_DOT = -1048576.0f;       // "no item": below every real dot (|dot| <= 1024)
 // item tiles per ring entry = per barrier: 16 MFMAs per wave and barrier for 512- and 256-bit codes
-template <int KS> struct EntryTiles { static constexpr int value = KS >= 4 ? 2 : 4; };
+constexpr int entry_tiles(int KS) { return KS >= 4 ? 2 : 4; }
+template <int KS> struct EntryTiles { static constexpr int value = entry_tiles(KS); };
+// the same for the two-workgroups-per-CU form of hamming_mfma_kernel (DB = false: one fragment set in 128 VGPRs)
+template <int KS> struct EntryTiles2 { static constexpr int value = KS >= 8 ? 1 : KS == 4 ? 2 : 4; };
+constexpr int ring_entries(bool db) { return db ? NBUF : 3; }
+// dynamic LDS of a sweep kernel: the ring of item tiles and, in the collect pass, the candidate columns behind it
+template <int KS, bool DB> constexpr int ring_bytes() {
+    return ring_entries(DB) * (DB ? EntryTiles<KS>::value : EntryTiles2<KS>::value) * KS * 1024;
+}
+constexpr size_t column_bytes(int cap) { return (size_t)WAVES * cap * 64 * sizeof(uint32_t); }
 
 // ---- sign planes ------------------------------------------------------------------------------------------------
 // 32 code bits -> 32 fp4 nibbles: bit b -> +1 (0x2) / -1 (0xA) = 0xA ^ (b << 3); four bits are spread to the nibble positions
@@ -177,6 +186,142 @@ __device__ __forceinline__ v16f sign_mfma_first(const v4i &a, const v4i &b, cons
     return d;
 }
 
+// ---- what the two sweep kernels share ------------------------------------------------------------------------------
+// the work of one workgroup: table slice `slice` (tiles t0 .. t1 - 1) against query block `qb`; wave wv holds query tile `qtile`
+struct SliceMap {
+    int slice, qb;
+    int64_t qtile, t0, t1;
+    int last_rel;           // first tile of the slice, relative to t0, that holds padding rows (zero nibbles)
+};
+__device__ __forceinline__ SliceMap slice_map(const HArgs &a, int wv) {
+    SliceMap m;
+    // XCD-aware block order: blocks b, b + 8, ... share an XCD (and its L2); give them consecutive logical ids so that
+    // an XCD sweeps one or two table slices, not all of them (bijective remap; speed only)
+    const int G = gridDim.x, b = blockIdx.x;
+    const int gq = G >> 3, gr = G & 7, xcd = b & 7;
+    const int logical = (xcd < gr ? xcd * (gq + 1) : gr * (gq + 1) + (xcd - gr) * gq) + (b >> 3);
+    m.slice = logical / a.nqb;
+    m.qb = logical - m.slice * a.nqb;
+    m.qtile = (int64_t)m.qb * WAVES + wv;
+    m.t0 = a.tile_begin + (int64_t)m.slice * a.tiles_per_slice;
+    m.t1 = m.t0 + a.tiles_per_slice;
+    if (m.t1 > a.tile_end) m.t1 = a.tile_end;
+    const int64_t last_tile = (a.N - 1) >> 5;               // tiles from here on hold padding rows
+    // the same bound relative to this slice, as a 32-bit scalar: a 64-bit signed compare is a VECTOR instruction on this ISA
+    // (v_cmp_lt_i64 + a move), two of the ~12 instructions every tile's epilogue pays
+    const int64_t last_rel64 = last_tile - m.t0;
+    m.last_rel = last_rel64 > 0x7fffffff ? 0x7fffffff : last_rel64 < 0 ? 0 : (int)last_rel64;
+    return m;
+}
+
+// Collect pass: the accumulators start at BIAS + r / 16 instead of 0 (r = register = row of the lane's 16), so an element
+// is v = BIAS + dot + r / 16: exact in f32 (|dot| <= 512, 4 fraction bits, v in [2560, 3585) = one binade), ordered by
+// (dot, r), and the maximum of a lane's 16 elements names its row: bits 12.. of the mantissa hold 1024 + dot, bits 8..11
+// r.  dot >= t  <=>  v >= BIAS + t for integers, so thresholds live in the same domain.
+constexpr float BIAS = 3072.0f;
+// a lane's state in front of the sweep: the accumulators' start values, the admission threshold (admit iff v >= thr) and, in
+// the bound pass, the KM largest group maxima of the dot, descending
+template <int MODE, int KM>
+__device__ __forceinline__ void sweep_start(const HArgs &a, int64_t q, v16f &cinit, float &thr, float (&best)[KM]) {
+    thr = 3.0e38f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) cinit[r] = MODE == 1 ? BIAS + (float)r * 0.0625f : 0.f;
+    if (MODE == 1) {
+        if (q < a.nq && !(PS_HM_DEBUG & 64)) thr = BIAS + (float)(a.nbits - 2 * a.thr0[q]);     // 64: nothing passes (the usual exit only)
+    } else {
+#pragma unroll
+        for (int j = 0; j < KM; ++j) best[j] = NO_DOT;
+    }
+}
+
+// exact: a lane's column of cnt keys ([slot][lane], slots beyond `upto` not looked at) -> its min(k, upto) smallest keys in slots
+// 0.., ascending (a serial selection in LDS); returns the new count min(cnt, k)
+__device__ __forceinline__ int select_smallest(uint32_t *cand, int lane, int cnt, int k, int upto) {
+    const int kk = k < upto ? k : upto;
+    for (int p = 0; p < kk; ++p) {
+        uint32_t bestk = (p < cnt) ? cand[p * 64 + lane] : EMPTY_KEY;
+        const uint32_t head = bestk;
+        int bj = p;
+        for (int j = p + 1; j < upto; ++j) {
+            const uint32_t v = (j < cnt) ? cand[j * 64 + lane] : EMPTY_KEY;
+            if (v < bestk) { bestk = v; bj = j; }
+        }
+        if (p < cnt) {
+            cand[bj * 64 + lane] = head;
+            cand[p * 64 + lane] = bestk;
+        }
+    }
+    return cnt < k ? cnt : k;
+}
+
+// maximum of the lane's 16 elements as a TERNARY tree (v_max3_f32): triples {0,1,2} .. {12,13,14} and {15}, then two
+// triples of those: 5 + 2 + 1 = 8 instructions (r03 first version: four groups of four, 8 + 3: collect 168 -> 159 us;
+// knock-outs: matrix work + these 8 maxima alone 115 us, with this exit only 125, everything 159)
+struct TileMax { float a0, a1, a2, a3, a4, a5, mu, mv, m; };
+__device__ __forceinline__ TileMax tile_maxima(const v16f &x) {
+    TileMax t;
+    t.a0 = fmaxf(fmaxf(x[0], x[1]), x[2]); t.a1 = fmaxf(fmaxf(x[3], x[4]), x[5]);
+    t.a2 = fmaxf(fmaxf(x[6], x[7]), x[8]); t.a3 = fmaxf(fmaxf(x[9], x[10]), x[11]);
+    t.a4 = fmaxf(fmaxf(x[12], x[13]), x[14]); t.a5 = x[15];
+    t.mu = fmaxf(fmaxf(t.a0, t.a1), t.a2); t.mv = fmaxf(fmaxf(t.a3, t.a4), t.a5);
+    t.m = fmaxf(t.mu, t.mv);
+    return t;
+}
+// A second element of the lane's 16 passes a threshold iff this value does (exact).  Two distinct rows differ in r / 3 or in r % 3, so a
+// second hit exists iff the second-largest maximum over the triples {3 j ..} (sg: the smaller of the two upper maxima or the
+// median of a triple of triples) or over the residue classes {r % 3 = j} (sh: the median of their three maxima) passes: 14 more
+// vector instructions.
+__device__ __forceinline__ float second_hit(const v16f &x, const TileMax &t) {
+    const float sg = fmaxf(fmaxf(fminf(t.mu, t.mv), __builtin_amdgcn_fmed3f(t.a0, t.a1, t.a2)), __builtin_amdgcn_fmed3f(t.a3, t.a4, t.a5));
+    const float h0 = fmaxf(fmaxf(fmaxf(x[0], x[3]), x[6]), fmaxf(fmaxf(x[9], x[12]), x[15]));
+    const float h1 = fmaxf(fmaxf(fmaxf(fmaxf(x[1], x[4]), x[7]), x[10]), x[13]);
+    const float h2 = fmaxf(fmaxf(fmaxf(fmaxf(x[2], x[5]), x[8]), x[11]), x[14]);
+    const float sh = __builtin_amdgcn_fmed3f(h0, h1, h2);
+    return fmaxf(sg, sh);
+}
+
+// bound pass: a new group maximum into the lane's descending list (insertion network, 2 KM instructions)
+template <int KM>
+__device__ __forceinline__ void bound_insert(float (&best)[KM], float x) {
+#pragma unroll
+    for (int j = 0; j < KM; ++j) {
+        const float hi = fmaxf(best[j], x);
+        x = fminf(best[j], x);
+        best[j] = hi;
+    }
+}
+
+// bound pass: a lane's list as group-minimum distances, ascending
+template <int KM>
+__device__ __forceinline__ void store_bound_list(const HArgs &a, int64_t q, int slice, int lh, const float (&best)[KM]) {
+    if (q >= a.nq) return;
+    int32_t *dst = a.bl + ((int64_t)q * (a.slices * 2) + slice * 2 + lh) * KM;
+#pragma unroll
+    for (int j = 0; j < KM; ++j) dst[j] = best[j] == NO_DOT ? 0x7fffffff : (a.nbits - (int)best[j]) >> 1;
+}
+
+// collect pass: the two lanes of a query (rows 4 lh + ... of every tile) merge their sorted columns of (distance << shift | row
+// in the slice) keys: one k-list per (slice, query)
+__device__ __forceinline__ void merge_lane_pair(const HArgs &a, const uint32_t *cand, int lane, int li, int lh, int64_t q, int cnt,
+                                                int slice, int64_t t0) {
+    ps_wave_lds_sync();
+    const int cnt_hi = __shfl(cnt, li + 32, 64);
+    if (q < a.nq && lh == 0) {
+        const uint32_t idmask = (1u << a.shift) - 1u;
+        const int64_t o = ((int64_t)(a.list_base + slice) * a.nq + q) * a.k;
+        int ia = 0, ib = 0;
+        for (int p = 0; p < a.k; ++p) {
+            const uint32_t ka = ia < cnt ? cand[ia * 64 + lane] : EMPTY_KEY;
+            const uint32_t kb = ib < cnt_hi ? cand[ib * 64 + lane + 32] : EMPTY_KEY;
+            const uint32_t key = ka < kb ? ka : kb;
+            if (ka < kb) ++ia; else ++ib;
+            const bool has = key != EMPTY_KEY;
+            a.out_d[o + p] = has ? (int32_t)(key >> a.shift) : 0x7fffffff;
+            a.out_r[o + p] = has ? (int32_t)((key & idmask) + (uint32_t)(t0 * 32)) : -1;
+        }
+    }
+}
+
 // MODE 0 = bound pass, 1 = collect pass.  One wave = one tile of 32 queries (16 query-fragment registers per 32 bits
 // of code).  Per-tile work besides the MFMAs is ~11 vector instructions (this file is compiled with -fno-honor-nans:
 // every value is an integer held in f32, so the maxima are bare v_max3_f32 without sNaN-quieting copies): the maximum of a
@@ -189,8 +334,8 @@ __device__ __forceinline__ v16f sign_mfma_first(const v4i &a, const v4i &b, cons
 template <int KS, int MODE, int KM, bool DB>
 __global__ __launch_bounds__(512, DB ? 2 : 4) void hamming_mfma_kernel(HArgs a) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
-    constexpr int IT = DB ? EntryTiles<KS>::value : (KS >= 8 ? 1 : KS == 4 ? 2 : 4);
-    constexpr int NB = DB ? NBUF : 3;
+    constexpr int IT = DB ? EntryTiles<KS>::value : EntryTiles2<KS>::value;
+    constexpr int NB = ring_entries(DB);
     constexpr int TILE_BYTES = KS * 1024;
     constexpr int ENTRY_BYTES = IT * TILE_BYTES;           // one ring entry = IT consecutive item tiles
     constexpr int PIECES = IT * KS;                        // 1 KiB LDS-DMA pieces per entry
@@ -200,26 +345,12 @@ __global__ __launch_bounds__(512, DB ? 2 : 4) void hamming_mfma_kernel(HArgs a) 
     const int li = lane & 31, lh = lane >> 5;
     const bool late = wv >= 4;                              // SIMD partners are waves w and w + 4
 
-    // XCD-aware block order: blocks b, b + 8, ... share an XCD (and its L2); give them consecutive logical ids so that
-    // an XCD sweeps one or two table slices, not all of them (bijective remap; speed only)
-    const int G = gridDim.x, b = blockIdx.x;
-    const int gq = G >> 3, gr = G & 7, xcd = b & 7;
-    const int logical = (xcd < gr ? xcd * (gq + 1) : gr * (gq + 1) + (xcd - gr) * gq) + (b >> 3);
-    const int slice = logical / a.nqb, qb = logical - slice * a.nqb;
-    const int64_t qtile = (int64_t)qb * WAVES + wv;
+    const SliceMap sm = slice_map(a, wv);
+    const int slice = sm.slice, last_rel = sm.last_rel;
+    const int64_t qtile = sm.qtile, t0 = sm.t0;
     const int64_t nqtiles = (a.nq + 31) >> 5;
     const int64_t q = qtile * 32 + li;
-    const bool q_ok = q < a.nq;
-
-    int64_t t0 = a.tile_begin + (int64_t)slice * a.tiles_per_slice;
-    int64_t t1 = t0 + a.tiles_per_slice;
-    if (t1 > a.tile_end) t1 = a.tile_end;
-    const int nt = t1 > t0 ? (int)((t1 - t0 + IT - 1) / IT) : 0;     // ring entries; t0 and tiles_per_slice are multiples of IT
-    const int64_t last_tile = (a.N - 1) >> 5;               // tiles from here on hold padding rows (zero nibbles)
-    // the same bound relative to this slice, as a 32-bit scalar: a 64-bit signed compare is a VECTOR instruction on this ISA
-    // (v_cmp_lt_i64 + a move), two of the ~12 instructions every tile's epilogue pays
-    const int64_t last_rel64 = last_tile - t0;
-    const int last_rel = last_rel64 > 0x7fffffff ? 0x7fffffff : last_rel64 < 0 ? 0 : (int)last_rel64;
+    const int nt = sm.t1 > t0 ? (int)((sm.t1 - t0 + IT - 1) / IT) : 0;     // ring entries; t0 and tiles_per_slice are multiples of IT
 
     // query fragments (B operand): 16 bytes per K step, resident for the whole sweep
     v4i bq[KS];
@@ -244,43 +375,17 @@ __global__ __launch_bounds__(512, DB ? 2 : 4) void hamming_mfma_kernel(HArgs a) 
 
     // ---- per-lane state ----
     const int CAP = a.cap;
-    uint32_t *cand = reinterpret_cast<uint32_t *>(smem + NB * ENTRY_BYTES) + wv * (CAP * 64);  // [slot][lane]
+    uint32_t *cand = reinterpret_cast<uint32_t *>(smem + ring_bytes<KS, DB>()) + wv * (CAP * 64);  // [slot][lane]
     int cnt = 0;
-    // Collect pass: the accumulators start at BIAS + r / 16 instead of 0 (r = register = row of the lane's 16), so an element
-    // is v = BIAS + dot + r / 16: exact in f32 (|dot| <= 512, 4 fraction bits, v in [2560, 3585) = one binade), ordered by
-    // (dot, r), and the maximum of a lane's 16 elements names its row: bits 12.. of the mantissa hold 1024 + dot, bits 8..11
-    // r.  dot >= t  <=>  v >= BIAS + t for integers, so thresholds live in the same domain.
-    constexpr float BIAS = 3072.0f;
-    float thr = 3.0e38f;                                    // admit iff v >= thr
-    float best[KM];                                         // bound pass: KM largest group maxima of the dot, descending
+    float thr, best[KM];
     v16f cinit;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) cinit[r] = MODE == 1 ? BIAS + (float)r * 0.0625f : 0.f;
-    if (MODE == 1) {
-        if (q_ok && !(PS_HM_DEBUG & 64)) thr = BIAS + (float)(a.nbits - 2 * a.thr0[q]);     // 64: nothing passes (the usual exit only)
-    } else {
-#pragma unroll
-        for (int j = 0; j < KM; ++j) best[j] = NO_DOT;
-    }
+    sweep_start<MODE>(a, q, cinit, thr, best);
 
     // a lane's column -> its k best keys in slots 0..k-1 (ascending), cnt = min(cnt, k); threshold tightened when the
     // column holds k keys: a later item (larger id) that only ties the k-th distance can never displace it
     auto compact = [&]() __attribute__((always_inline)) {
         const int k = a.k;
-        for (int p = 0; p < k; ++p) {
-            uint32_t bestk = (p < cnt) ? cand[p * 64 + lane] : EMPTY_KEY;
-            const uint32_t head = bestk;
-            int bj = p;
-            for (int j = p + 1; j < CAP; ++j) {
-                const uint32_t v = (j < cnt) ? cand[j * 64 + lane] : EMPTY_KEY;
-                if (v < bestk) { bestk = v; bj = j; }
-            }
-            if (p < cnt) {
-                cand[bj * 64 + lane] = head;
-                cand[p * 64 + lane] = bestk;
-            }
-        }
-        cnt = cnt < k ? cnt : k;
+        cnt = select_smallest(cand, lane, cnt, k, CAP);
         if (cnt == k) {
             const int hk = (int)(cand[(k - 1) * 64 + lane] >> a.shift);
             const float nthr = BIAS + (float)(a.nbits - 2 * hk + 2);
@@ -302,13 +407,12 @@ __global__ __launch_bounds__(512, DB ? 2 : 4) void hamming_mfma_kernel(HArgs a) 
             // what the matrix work costs.  collect 115 us (whole epilogue 159, usual exit only 125).  A build whose epilogue does NOT
             // read them (bit 1, or ten unrelated vector instructions) lets the compiler drop every MFMA whose result is overwritten
             // unread: its 58 / 67 us are the ring and the barriers, not a matrix-pipe floor (r03's first reading of bit 1 was wrong)
-            const float a0 = fmaxf(fmaxf(acc[0], acc[1]), acc[2]), a1 = fmaxf(fmaxf(acc[3], acc[4]), acc[5]);
-            const float a2 = fmaxf(fmaxf(acc[6], acc[7]), acc[8]), a3 = fmaxf(fmaxf(acc[9], acc[10]), acc[11]);
-            const float a4 = fmaxf(fmaxf(acc[12], acc[13]), acc[14]), a5 = acc[15];
-            dbg_sink = fmaxf(dbg_sink, fmaxf(fmaxf(fmaxf(a0, a1), a2), fmaxf(fmaxf(a3, a4), a5)));
+            dbg_sink = fmaxf(dbg_sink, tile_maxima(acc).m);
             return;
         }
         const int64_t t = t0 + i;
+        // (hamming_pipe_kernel's mask_padding, written out: as a shared function it cost hamming_mfma_kernel<8, *, 4, false> four to
+        // thirty registers -- two spilled in the collect pass -- although the source is the same)
         if (__builtin_expect(i >= last_rel, 0)) {           // wave-uniform, once per table: mask the padding rows of its end
             const int64_t left64 = a.N - t * 32;            // valid rows of this tile (<= 0: a padding tile of the last entry)
             const int left = (int)(left64 < 0 ? 0 : left64 > 32 ? 32 : left64) - 4 * lh;
@@ -316,25 +420,13 @@ __global__ __launch_bounds__(512, DB ? 2 : 4) void hamming_mfma_kernel(HArgs a) 
             for (int r = 0; r < 16; ++r)
                 if ((r & 3) + 8 * (r >> 2) >= left) acc[r] = MODE == 1 ? 0.f : NO_DOT;
         }
-        // maximum of the lane's 16 elements as a TERNARY tree (v_max3_f32): triples {0,1,2} .. {12,13,14} and {15}, then two
-        // triples of those: 5 + 2 + 1 = 8 instructions (r03 first version: four groups of four, 8 + 3: collect 168 -> 159 us;
-        // knock-outs: matrix work + these 8 maxima alone 115 us, with this exit only 125, everything 159)
-        const float a0 = fmaxf(fmaxf(acc[0], acc[1]), acc[2]), a1 = fmaxf(fmaxf(acc[3], acc[4]), acc[5]);
-        const float a2 = fmaxf(fmaxf(acc[6], acc[7]), acc[8]), a3 = fmaxf(fmaxf(acc[9], acc[10]), acc[11]);
-        const float a4 = fmaxf(fmaxf(acc[12], acc[13]), acc[14]), a5 = acc[15];
-        const float mu = fmaxf(fmaxf(a0, a1), a2), mv = fmaxf(fmaxf(a3, a4), a5);
-        const float m = fmaxf(mu, mv);
+        const TileMax tm = tile_maxima(acc);
+        const float m = tm.m;
         if (MODE == 0) {
             // a lane's list changes only when its new group maximum beats the list's last entry: after the first few
             // tiles that is rare, and the insertion network (2 KM instructions) runs for the whole wave only then
             if (__ballot(m > best[KM - 1]) == 0ull) return;
-            float x = m;
-#pragma unroll
-            for (int j = 0; j < KM; ++j) {
-                const float hi = fmaxf(best[j], x);
-                x = fminf(best[j], x);
-                best[j] = hi;
-            }
+            bound_insert(best, m);
             return;
         }
         PS_HM_COUNT(0, 1);
@@ -344,21 +436,15 @@ __global__ __launch_bounds__(512, DB ? 2 : 4) void hamming_mfma_kernel(HArgs a) 
         // 64 x 16.  Every scalar branch on a vector compare costs this wave a round trip that its SIMD partner's MFMA stream
         // does not hide (the r02 version walked groups and rows with ~12 such branches: ~900 cycles per entry, 2/3 of the
         // collect pass), so the common case is straight-line: the maximum itself names its row (fraction bits) and is
-        // appended; that is complete unless a second element of the lane passes too.  Two distinct rows differ in r / 3 or in
-        // r % 3, so a second hit exists iff the second-largest maximum over the triples {3 j ..} (sg: the smaller of the two
-        // upper maxima or the median of a triple of triples) or over the residue classes {r % 3 = j} (sh: the median of their
-        // three maxima) passes: 14 more vector instructions, one branch, and only then the walk over all rows.
-        const float sg = fmaxf(fmaxf(fminf(mu, mv), __builtin_amdgcn_fmed3f(a0, a1, a2)), __builtin_amdgcn_fmed3f(a3, a4, a5));
-        const float h0 = fmaxf(fmaxf(fmaxf(acc[0], acc[3]), acc[6]), fmaxf(fmaxf(acc[9], acc[12]), acc[15]));
-        const float h1 = fmaxf(fmaxf(fmaxf(fmaxf(acc[1], acc[4]), acc[7]), acc[10]), acc[13]);
-        const float h2 = fmaxf(fmaxf(fmaxf(fmaxf(acc[2], acc[5]), acc[8]), acc[11]), acc[14]);
-        const float sh = __builtin_amdgcn_fmed3f(h0, h1, h2);
+        // appended; that is complete unless a second element of the lane passes too (second_hit: 14 more vector instructions),
+        // one branch, and only then the walk over all rows.
+        const float second = second_hit(acc, tm);
         const uint32_t base = (uint32_t)i * 32u + 4u * lh;
         // Room in the columns (r04, see hamming_pipe_kernel): the usual tile appends ONE key per lane, so after a tile only room for
         // one more is demanded; a walk counts what it is about to append and compacts first only if a column would overflow.
         // (Demanding room for 16 rows after every tile made ~60 of a launch's 480 workgroups compact -- a serial selection in LDS,
         // ~30 K cycles with the workgroup at its barrier -- and those workgroups set the kernel's time.)
-        if (__ballot(fmaxf(sg, sh) >= thr) == 0ull) {
+        if (__ballot(second >= thr) == 0ull) {
             if (m >= thr) append_bits(__float_as_uint(m), base);
         } else {
             PS_HM_COUNT(2, 1);
@@ -493,31 +579,11 @@ __global__ __launch_bounds__(512, DB ? 2 : 4) void hamming_mfma_kernel(HArgs a) 
 
     // ---- results ----
     if (MODE == 0) {
-        if (q_ok) {
-            int32_t *dst = a.bl + ((int64_t)q * (a.slices * 2) + slice * 2 + lh) * KM;
-#pragma unroll
-            for (int j = 0; j < KM; ++j) dst[j] = best[j] == NO_DOT ? 0x7fffffff : (a.nbits - (int)best[j]) >> 1;
-        }
+        store_bound_list(a, q, slice, lh, best);
         return;
     }
-    // the two lanes of a query (rows 4 lh + ... of every tile) merge their sorted columns: one k-list per (slice, query)
     compact();
-    ps_wave_lds_sync();
-    const int cnt_hi = __shfl(cnt, li + 32, 64);
-    if (q_ok && lh == 0) {
-        const uint32_t idmask = (1u << a.shift) - 1u;
-        const int64_t o = ((int64_t)(a.list_base + slice) * a.nq + q) * a.k;
-        int ia = 0, ib = 0;
-        for (int p = 0; p < a.k; ++p) {
-            const uint32_t ka = ia < cnt ? cand[ia * 64 + lane] : EMPTY_KEY;
-            const uint32_t kb = ib < cnt_hi ? cand[ib * 64 + lane + 32] : EMPTY_KEY;
-            const uint32_t key = ka < kb ? ka : kb;
-            if (ka < kb) ++ia; else ++ib;
-            const bool has = key != EMPTY_KEY;
-            a.out_d[o + p] = has ? (int32_t)(key >> a.shift) : 0x7fffffff;
-            a.out_r[o + p] = has ? (int32_t)((key & idmask) + (uint32_t)(t0 * 32)) : -1;
-        }
-    }
+    merge_lane_pair(a, cand, lane, li, lh, q, cnt, slice, t0);
 }
 
 // ---- r04: the same two passes as ONE software pipeline per wave -----------------------------------------------------------------
@@ -536,6 +602,7 @@ __global__ __launch_bounds__(512, DB ? 2 : 4) void hamming_mfma_kernel(HArgs a) 
 // workgroups per CU)
 template <int KS> struct PipeServed { static constexpr bool value = KS == 4 || KS == 8; };
 template <int KS> struct PipeRing { static constexpr int value = KS <= 4 ? 24 / KS : 3; };
+template <int KS> constexpr int pipe_ring_bytes() { return PipeRing<KS>::value * KS * 1024; }
 
 template <int KS, int MODE>
 __global__ __launch_bounds__(512, 4) void hamming_pipe_kernel(HArgs a) {
@@ -552,22 +619,11 @@ __global__ __launch_bounds__(512, 4) void hamming_pipe_kernel(HArgs a) {
     const unsigned long long ps_t_start = __builtin_readcyclecounter();
 #endif
 
-    const int G = gridDim.x, b = blockIdx.x;                // XCD-aware block order (see hamming_mfma_kernel)
-    const int gq = G >> 3, gr = G & 7, xcd = b & 7;
-    const int logical = (xcd < gr ? xcd * (gq + 1) : gr * (gq + 1) + (xcd - gr) * gq) + (b >> 3);
-    const int slice = logical / a.nqb, qb = logical - slice * a.nqb;
-    const int64_t qtile = (int64_t)qb * WAVES + wv;
+    const SliceMap sm = slice_map(a, wv);
+    const int slice = sm.slice, last_rel = sm.last_rel;
+    const int64_t qtile = sm.qtile, t0 = sm.t0;
     const int64_t nqtiles = (a.nq + 31) >> 5;
-    const int64_t q = qtile * 32 + li;
-    const bool q_ok = q < a.nq;
-
-    int64_t t0 = a.tile_begin + (int64_t)slice * a.tiles_per_slice;
-    int64_t t1 = t0 + a.tiles_per_slice;
-    if (t1 > a.tile_end) t1 = a.tile_end;
-    const int nt = t1 > t0 ? (int)(t1 - t0) : 0;            // tiles of this slice (the plane table is padded to whole PAD_TILES)
-    const int64_t last_tile = (a.N - 1) >> 5;               // tiles from here on hold padding rows
-    const int64_t last_rel64 = last_tile - t0;
-    const int last_rel = last_rel64 > 0x7fffffff ? 0x7fffffff : last_rel64 < 0 ? 0 : (int)last_rel64;
+    const int nt = sm.t1 > t0 ? (int)(sm.t1 - t0) : 0;      // tiles of this slice (the plane table is padded to whole PAD_TILES)
     const int n_main = (last_rel < nt ? last_rel : nt) & ~1;  // leading tiles free of padding rows, an even number
 
     v4i bq[KS];
@@ -583,20 +639,11 @@ __global__ __launch_bounds__(512, 4) void hamming_pipe_kernel(HArgs a) {
     };
 
     const int CAP = a.cap;
-    uint32_t *cand = reinterpret_cast<uint32_t *>(smem + NB * TILE_BYTES) + wv * (CAP * 64);  // [slot][lane]
+    uint32_t *cand = reinterpret_cast<uint32_t *>(smem + pipe_ring_bytes<KS>()) + wv * (CAP * 64);  // [slot][lane]
     int cnt = 0;
-    constexpr float BIAS = 3072.0f;                         // see hamming_mfma_kernel: v = BIAS + dot + r / 16
-    float thr = 3.0e38f;
-    float best[KM];
+    float thr, best[KM];
     v16f cinit;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) cinit[r] = MODE == 1 ? BIAS + (float)r * 0.0625f : 0.f;
-    if (MODE == 1) {
-        if (q_ok && !(PS_HM_DEBUG & 64)) thr = BIAS + (float)(a.nbits - 2 * a.thr0[q]);     // 64: nothing passes (the usual exit only)
-    } else {
-#pragma unroll
-        for (int j = 0; j < KM; ++j) best[j] = NO_DOT;
-    }
+    sweep_start<MODE>(a, qtile * 32 + li, cinit, thr, best);
     // Candidate keys of this kernel: [2047 - d (11 bits) | tile index in the slice (17 bits) | r (4 bits)] with d = 1024 + dot and r the
     // row code of the element -- three fields cut straight out of the element's float bits (v = 2048 + d + r / 16 has d in mantissa
     // bits 12..22 and r in bits 8..11: a shift, a bit-field extract, a bit-field insert and an inversion instead of the nine
@@ -618,22 +665,7 @@ __global__ __launch_bounds__(512, 4) void hamming_pipe_kernel(HArgs a) {
     // the wave); the threshold is tightened when the column holds k keys
     auto compact = [&]() __attribute__((always_inline)) {
         const int k = a.k;
-        const int mx = wave_max(cnt);
-        const int kk = k < mx ? k : mx;
-        for (int p = 0; p < kk; ++p) {
-            uint32_t bestk = (p < cnt) ? cand[p * 64 + lane] : EMPTY_KEY;
-            const uint32_t head = bestk;
-            int bj = p;
-            for (int j = p + 1; j < mx; ++j) {
-                const uint32_t v = (j < cnt) ? cand[j * 64 + lane] : EMPTY_KEY;
-                if (v < bestk) { bestk = v; bj = j; }
-            }
-            if (p < cnt) {
-                cand[bj * 64 + lane] = head;
-                cand[p * 64 + lane] = bestk;
-            }
-        }
-        cnt = cnt < k ? cnt : k;
+        cnt = select_smallest(cand, lane, cnt, k, wave_max(cnt));
         if (cnt == k) {                                     // only a strictly larger dot can still enter: d >= d_k + 2 (dots share their parity)
             const int dk = 2047 - (int)(cand[(k - 1) * 64 + lane] >> 21);
             const float nthr = (float)(2048 + dk + 2);
@@ -707,13 +739,7 @@ __global__ __launch_bounds__(512, 4) void hamming_pipe_kernel(HArgs a) {
     auto finish = [&](const v16f &acc, const Det &d, int i) __attribute__((always_inline)) {
         if (d.any == 0ull) return;
         if (MODE == 0) {
-            float x = d.m;
-#pragma unroll
-            for (int j = 0; j < KM; ++j) {
-                const float hi = fmaxf(best[j], x);
-                x = fminf(best[j], x);
-                best[j] = hi;
-            }
+            bound_insert(best, d.m);
             return;
         }
         const uint32_t base = (uint32_t)i << 4;
@@ -758,27 +784,21 @@ __global__ __launch_bounds__(512, 4) void hamming_pipe_kernel(HArgs a) {
         }
         if (cmax > CAP - 1) make_room(1);
     };
-    // A second hit of a lane in this tile (exact, see hamming_mfma_kernel): two distinct rows differ in r / 3 or in r % 3, so it
-    // exists iff the second-largest maximum over the triples {3 j ..} (sg) or over the residue classes {r % 3 = j} (sh) passes.
-#define PS_MAX3(A, B, C) fmaxf(fmaxf(A, B), C)
+    // the detection of a tile outside the pipeline (a slice's last tile)
     auto detect_all = [&](const v16f &x, Det &d) __attribute__((always_inline)) {
-        const float a0 = PS_MAX3(x[0], x[1], x[2]), a1 = PS_MAX3(x[3], x[4], x[5]), a2 = PS_MAX3(x[6], x[7], x[8]);
-        const float a3 = PS_MAX3(x[9], x[10], x[11]), a4 = PS_MAX3(x[12], x[13], x[14]), a5 = x[15];
-        const float mu = PS_MAX3(a0, a1, a2), mv = PS_MAX3(a3, a4, a5);
-        d.m = fmaxf(mu, mv);
+        const TileMax tm = tile_maxima(x);
+        d.m = tm.m;
         d.appended = false;
         if (MODE == 0) { d.any = __ballot(d.m > best[KM - 1]); d.any2 = 0ull; return; }
         d.any = __ballot(d.m >= thr);
-        const float sg = PS_MAX3(fminf(mu, mv), __builtin_amdgcn_fmed3f(a0, a1, a2), __builtin_amdgcn_fmed3f(a3, a4, a5));
-        const float h0 = fmaxf(PS_MAX3(x[0], x[3], x[6]), PS_MAX3(x[9], x[12], x[15]));
-        const float h1 = PS_MAX3(PS_MAX3(x[1], x[4], x[7]), x[10], x[13]);
-        const float h2 = PS_MAX3(PS_MAX3(x[2], x[5], x[8]), x[11], x[14]);
-        d.any2 = __ballot(fmaxf(sg, __builtin_amdgcn_fmed3f(h0, h1, h2)) >= thr);
+        d.any2 = __ballot(second_hit(x, tm) >= thr);
     };
     // the MFMA chain of one tile into `w`, the detection of the previous tile `x` in its gaps: 23 vector instructions behind the
     // first four MFMAs (the gap of a 32 x 32 x 64 fp4 MFMA leaves room for about six).  sched_barrier(0) pins the interleaving;
     // PIN: an empty volatile asm that names the accumulator keeps each MFMA at its place -- the results are not needed before the
     // next tile's detection, and without it the compiler sinks the whole chain below the branches of `finish`.
+    // (tile_maxima and second_hit, written out: they are cut into pieces that sit between the MFMAs)
+#define PS_MAX3(A, B, C) fmaxf(fmaxf(A, B), C)
 #define PS_PIN(W) asm volatile("" : "+v"(W))
     // The usual hit (one passing element per lane: its maximum) is appended right there, predicated, between the third and the
     // fourth MFMA: every wave of the workgroup then runs the same instructions tile after tile whether it has a hit or not, and
@@ -932,13 +952,8 @@ __global__ __launch_bounds__(512, 4) void hamming_pipe_kernel(HArgs a) {
     asm volatile("" : "+v"(tid2));
     const int li2 = tid2 & 31, lh2 = (tid2 >> 5) & 1, lane2 = tid2 & 63;
     const int64_t q2 = qtile * 32 + li2;
-    const bool q2_ok = q2 < a.nq;
     if (MODE == 0) {
-        if (q2_ok) {
-            int32_t *dst = a.bl + ((int64_t)q2 * (a.slices * 2) + slice * 2 + lh2) * KM;
-#pragma unroll
-            for (int j = 0; j < KM; ++j) dst[j] = best[j] == NO_DOT ? 0x7fffffff : (a.nbits - (int)best[j]) >> 1;
-        }
+        store_bound_list(a, q2, slice, lh2, best);
         return;
     }
 #if PS_HM_DEBUG & 512
@@ -948,7 +963,7 @@ __global__ __launch_bounds__(512, 4) void hamming_pipe_kernel(HArgs a) {
     if (MODE == 1 && tid == 0 && blockIdx.x < 4096) {
         ps_hm_times[4 * blockIdx.x] = ps_t_start; ps_hm_times[4 * blockIdx.x + 1] = __builtin_readcyclecounter();
         atomicOr(&ps_hm_times[4 * blockIdx.x + 2], (unsigned long long)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 4));      // HW_ID
-        ps_hm_times[4 * blockIdx.x + 3] = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20) | ((unsigned long long)slice << 32) | ((unsigned long long)qb << 48);   // XCC_ID, slice, query block
+        ps_hm_times[4 * blockIdx.x + 3] = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 20) | ((unsigned long long)slice << 32) | ((unsigned long long)sm.qb << 48);   // XCC_ID, slice, query block
     }
 #endif
     compact();
@@ -958,22 +973,7 @@ __global__ __launch_bounds__(512, 4) void hamming_pipe_kernel(HArgs a) {
         const uint32_t r = key & 15u, tile = (key >> 4) & 0x1ffffu;
         cand[p * 64 + lane2] = ((uint32_t)((a.nbits - dot) >> 1) << a.shift) | (tile * 32u + 4u * lh2 + (r & 3u) + 8u * (r >> 2));
     }
-    ps_wave_lds_sync();
-    const int cnt_hi = __shfl(cnt, li2 + 32, 64);
-    if (q2_ok && lh2 == 0) {
-        const uint32_t idmask = (1u << a.shift) - 1u;
-        const int64_t o = ((int64_t)(a.list_base + slice) * a.nq + q2) * a.k;
-        int ia = 0, ib = 0;
-        for (int p = 0; p < a.k; ++p) {
-            const uint32_t ka = ia < cnt ? cand[ia * 64 + lane2] : EMPTY_KEY;
-            const uint32_t kb = ib < cnt_hi ? cand[ib * 64 + lane2 + 32] : EMPTY_KEY;
-            const uint32_t key = ka < kb ? ka : kb;
-            if (ka < kb) ++ia; else ++ib;
-            const bool has = key != EMPTY_KEY;
-            a.out_d[o + p] = has ? (int32_t)(key >> a.shift) : 0x7fffffff;
-            a.out_r[o + p] = has ? (int32_t)((key & idmask) + (uint32_t)(t0 * 32)) : -1;
-        }
-    }
+    merge_lane_pair(a, cand, lane2, li2, lh2, q2, cnt, slice, t0);
 }
 
 // Final merge of the per-slice lists: 16 lanes per query, lane j = the head of slice j's sorted list; k rounds of
@@ -1019,21 +1019,7 @@ __global__ __launch_bounds__(256) void slice_merge_kernel(const int32_t *__restr
 }
 
 // the same merge for up to 64 lists (few queries over a large table are cut into more slices, so that they still fill the
-// chip): one wave per query, lane j = the head of list j, wave minimum by DPP + v_readlane
-__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
-#define PS_STEP(ctrl, rows)                                                                                     \
-    {                                                                                                           \
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)(uint32_t)v, ctrl, rows, 0xf, false); \
-        const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)(uint32_t)(v >> 32), ctrl, rows, 0xf, false); \
-        const uint64_t o = ((uint64_t)hi << 32) | lo;                                                           \
-        v = o < v ? o : v;                                                                                      \
-    }
-    PS_STEP(0xB1, 0xf) PS_STEP(0x4E, 0xf) PS_STEP(0x141, 0xf) PS_STEP(0x140, 0xf) PS_STEP(0x142, 0xa) PS_STEP(0x143, 0xc)
-#undef PS_STEP
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63);
-    return ((uint64_t)hi << 32) | lo;
-}
+// chip): one wave per query, lane j = the head of list j, wave minimum by DPP + v_readlane (ps_wave_min_u64)
 __global__ __launch_bounds__(256) void slice_merge64_kernel(const int32_t *__restrict__ din, const int32_t *__restrict__ rin,
                                                             int P, int64_t nq, int k, int64_t id_offset,
                                                             int32_t *__restrict__ dout, int64_t *__restrict__ iout) {
@@ -1051,7 +1037,7 @@ __global__ __launch_bounds__(256) void slice_merge64_kernel(const int32_t *__res
     int ptr = 0;
     uint64_t key = head(0);
     for (int r = 0; r < k; ++r) {
-        const uint64_t m = wave_min_u64(key);
+        const uint64_t m = ps_wave_min_u64(key);
         if (lane == 0) {
             dout[q * k + r] = m == NONE ? 0x7fffffff : (int32_t)(m >> 32);
             iout[q * k + r] = m == NONE ? -1 : (int64_t)(uint32_t)m + id_offset;
@@ -1105,6 +1091,21 @@ int key_shift_bits(int nbits) {
     return 32 - dbits;
 }
 
+// 16-byte pieces of the plane table of n codes: whole ring entries (the padding tiles are zero-filled)
+int64_t plane_pieces(int64_t n, int KS) { return (((n + 31) / 32 + PAD_TILES - 1) / PAD_TILES * PAD_TILES) * KS * 64; }
+
+int launch_expand(const uint32_t *codes, int64_t n, int KS, void *planes, hipStream_t st) {
+    const int64_t pieces = plane_pieces(n, KS);
+    int64_t grid = ps_cdiv(pieces, 256);
+    if (grid > 256 * 64) grid = 256 * 64;
+    hipLaunchKernelGGL(lsh_expand_kernel, dim3((unsigned)grid), dim3(256), 0, st, codes, n, KS, pieces, reinterpret_cast<uint4 *>(planes));
+    PS_CHECK_LAUNCH();
+    return PS_OK;
+}
+
+// slots of a lane's candidate column: k kept + one tile's 16 rows (k <= 32 with one workgroup per CU, k <= 12 with two)
+constexpr int column_cap(bool db, int k) { return db ? (k <= 16 ? 32 : 48) : 28; }
+
 struct Plan {
     bool ok;
     int KS, IT, nqb, slices, bslices, shift, km, cap;
@@ -1127,10 +1128,10 @@ Plan make_plan(int64_t nq, int64_t N, int cs, int k) {
     if (!(p.KS == 1 || p.KS == 2 || p.KS == 4 || p.KS == 8)) return p;
     if (k <= 0 || k > 32) return p;
     if (nq < 64 || N < 4096) return p;                    // small problems: the popcount kernel has no tile padding
-    const int IT = p.KS >= 4 ? 2 : 4;                      // EntryTiles<KS>
+    const int IT = entry_tiles(p.KS);
     p.IT = IT;
     p.db = k > 12 || p.KS <= 2 || env_int("PS_HAMMING_MFMA_DB", 0) != 0;   // (KS <= 2: four tiles per entry do not fit 128 VGPRs)
-    p.cap = p.db ? (k <= 16 ? 32 : 48) : 28;               // a lane's column: k kept + one tile's 16 rows
+    p.cap = column_cap(p.db, k);
     p.shift = key_shift_bits(cs * 8);
     p.tiles = (N + 31) >> 5;
     const int64_t nqt = (nq + 31) >> 5;
@@ -1186,74 +1187,74 @@ bool allow_lds(K kernel, size_t bytes) {
            hipSuccess;
 }
 
+// The sweep kernel of one pass (0 bound, 1 collect) and its dynamic LDS.  Two workgroups per CU (!p.db: k <= 12, 256- / 512-bit
+// codes) run the pipelined kernel, or with pipe = false its predecessor; their bound pass keeps four values per lane, so a
+// plan that wants longer lists takes its bound from the one-workgroup kernel.  nullptr: no kernel for this plan.
+struct Sweep {
+    void (*kernel)(HArgs);
+    size_t lds;
+};
+template <int KS>
+Sweep pick_sweep(int pass, const Plan &p, bool pipe) {
+    const size_t cols = pass == 1 ? column_bytes(p.cap) : 0;
+    if (!p.db && (pass == 1 || p.km == 4)) {
+        if constexpr (PipeServed<KS>::value)
+            if (pipe) return {pass == 1 ? hamming_pipe_kernel<KS, 1> : hamming_pipe_kernel<KS, 0>, pipe_ring_bytes<KS>() + cols};
+        if constexpr (KS >= 4)
+            return {pass == 1 ? hamming_mfma_kernel<KS, 1, 4, false> : hamming_mfma_kernel<KS, 0, 4, false>, ring_bytes<KS, false>() + cols};
+    }
+    const size_t lds = ring_bytes<KS, true>() + cols;
+    if (pass == 1) return {hamming_mfma_kernel<KS, 1, 4, true>, lds};
+    if (p.km == 4) return {hamming_mfma_kernel<KS, 0, 4, true>, lds};
+    if (p.km == 16) return {hamming_mfma_kernel<KS, 0, 16, true>, lds};
+    if constexpr (KS < 8)
+        if (p.km == 32) return {hamming_mfma_kernel<KS, 0, 32, true>, lds};
+    return {nullptr, 0};
+}
+
 template <int KS>
 int launch_passes(const Plan &p, HArgs a, hipStream_t st, int32_t *thr0, int32_t *bl, int64_t nq, void *qp_ws) {
-    constexpr int IT = EntryTiles<KS>::value;
-    constexpr int IT1 = KS >= 8 ? 1 : KS == 4 ? 2 : 4;      // entry of the two-workgroups-per-CU collect kernel
-    const size_t tiles_lds = (size_t)NBUF * IT * KS * 1024;
-    const size_t lds = p.db ? tiles_lds + (size_t)WAVES * p.cap * 64 * sizeof(uint32_t)
-                            : (size_t)3 * IT1 * KS * 1024 + (size_t)WAVES * p.cap * 64 * sizeof(uint32_t);
     // once per (kernel, device): one process may drive several GPUs
     static PsPerDevice lds_done;
     int devid = 0;
     if (hipGetDevice(&devid) != hipSuccess || devid < 0 || devid >= 64) return PS_ELAUNCH;
     bool lds_ok = lds_done.get(devid) != 0;
     if (!lds_ok) {
-        lds_ok = allow_lds(hamming_mfma_kernel<KS, 0, 4, true>, 160 * 1024) && allow_lds(hamming_mfma_kernel<KS, 0, 16, true>, 160 * 1024) &&
-                 allow_lds(hamming_mfma_kernel<KS, 1, 4, true>, 160 * 1024);
-        if constexpr (KS < 8) lds_ok = lds_ok && allow_lds(hamming_mfma_kernel<KS, 0, 32, true>, 160 * 1024);
+        // the most a kernel form is ever launched with: 160 KiB at 512 bit with one workgroup per CU, 80 KiB with two
+        constexpr size_t lds1 = ring_bytes<KS, true>() + column_bytes(column_cap(true, 32));
+        constexpr size_t cols2 = column_bytes(column_cap(false, 12));
+        lds_ok = allow_lds(hamming_mfma_kernel<KS, 0, 4, true>, lds1) && allow_lds(hamming_mfma_kernel<KS, 0, 16, true>, lds1) &&
+                 allow_lds(hamming_mfma_kernel<KS, 1, 4, true>, lds1);
+        if constexpr (KS < 8) lds_ok = lds_ok && allow_lds(hamming_mfma_kernel<KS, 0, 32, true>, lds1);
         // two workgroups per CU: 256- and 512-bit codes only (make_plan: KS <= 2 always takes the one-workgroup form, whose
         // four-tile entries do not fit 128 VGPRs -- those instantiations spilled and were never launched: not built any more)
         if constexpr (KS >= 4)
-            lds_ok = lds_ok && allow_lds(hamming_mfma_kernel<KS, 1, 4, false>, 80 * 1024) && allow_lds(hamming_mfma_kernel<KS, 0, 4, false>, 80 * 1024);
+            lds_ok = lds_ok && allow_lds(hamming_mfma_kernel<KS, 1, 4, false>, ring_bytes<KS, false>() + cols2) &&
+                     allow_lds(hamming_mfma_kernel<KS, 0, 4, false>, ring_bytes<KS, false>() + cols2);
         if constexpr (PipeServed<KS>::value)
-            lds_ok = lds_ok && allow_lds(hamming_pipe_kernel<KS, 1>, 80 * 1024) && allow_lds(hamming_pipe_kernel<KS, 0>, 80 * 1024);
+            lds_ok = lds_ok && allow_lds(hamming_pipe_kernel<KS, 1>, pipe_ring_bytes<KS>() + cols2) &&
+                     allow_lds(hamming_pipe_kernel<KS, 0>, pipe_ring_bytes<KS>() + cols2);
         lds_done.set(devid, lds_ok ? 1 : 0);
     }
     if (!lds_ok) return PS_ELAUNCH;
     a.nqb = p.nqb;
     a.cap = p.cap;
-    // bound
-    HArgs b = a;
-    b.tile_begin = 0; b.tile_end = p.sample_tiles; b.tiles_per_slice = p.btiles_per_slice; b.slices = p.bslices; b.bl = bl;
-    const unsigned gb = (unsigned)(p.nqb * p.bslices);
-    bool launched = false;
     // 0: the r03 kernels (cross-check / experiments); the pipelined kernels' keys hold a 17-bit tile index per slice
     const bool pipe = PipeServed<KS>::value && env_int("PS_HAMMING_PIPE", 1) != 0 && p.tiles_per_slice <= (1 << 17) && p.btiles_per_slice <= (1 << 17);
     // packed query codes are expanded by the pipelined kernels' workgroups themselves; when either pass runs a kernel that reads
     // planes (k > 12, 64- / 128-bit codes, PS_HAMMING_PIPE=0) the launcher builds them in the workspace first
     if (a.qplanes == nullptr && !(pipe && !p.db && p.km == 4)) {
-        const int64_t pieces = (((nq + 31) / 32 + PAD_TILES - 1) / PAD_TILES * PAD_TILES) * KS * 64;
-        int64_t ge = ps_cdiv(pieces, 256);
-        if (ge > 256 * 64) ge = 256 * 64;
-        hipLaunchKernelGGL(lsh_expand_kernel, dim3((unsigned)ge), dim3(256), 0, st, a.qcodes, nq, KS, pieces, reinterpret_cast<uint4 *>(qp_ws));
-        PS_CHECK_LAUNCH();
+        const int rc = launch_expand(a.qcodes, nq, KS, qp_ws, st);
+        if (rc != PS_OK) return rc;
         a.qplanes = reinterpret_cast<const unsigned char *>(qp_ws);
         a.qcodes = nullptr;
-        b.qplanes = a.qplanes;
-        b.qcodes = nullptr;
     }
-    if constexpr (PipeServed<KS>::value) {
-        if (p.km == 4 && !p.db && pipe) {
-            hipLaunchKernelGGL((hamming_pipe_kernel<KS, 0>), dim3(gb), dim3(512), (size_t)PipeRing<KS>::value * KS * 1024, st, b);
-            launched = true;
-        }
-    }
-    if constexpr (KS >= 4) {
-        if (!launched && p.km == 4 && !p.db) {
-            hipLaunchKernelGGL((hamming_mfma_kernel<KS, 0, 4, false>), dim3(gb), dim3(512), (size_t)3 * IT1 * KS * 1024, st, b);
-            launched = true;
-        }
-    }
-    if constexpr (KS < 8) {
-        if (!launched && p.km == 32) {
-            hipLaunchKernelGGL((hamming_mfma_kernel<KS, 0, 32, true>), dim3(gb), dim3(512), tiles_lds, st, b);
-            launched = true;
-        }
-    }
-    if (!launched && p.km == 4) hipLaunchKernelGGL((hamming_mfma_kernel<KS, 0, 4, true>), dim3(gb), dim3(512), tiles_lds, st, b);
-    else if (!launched && p.km == 16) hipLaunchKernelGGL((hamming_mfma_kernel<KS, 0, 16, true>), dim3(gb), dim3(512), tiles_lds, st, b);
-    else if (!launched) return PS_EINVAL;
+    // bound
+    HArgs b = a;
+    b.tile_begin = 0; b.tile_end = p.sample_tiles; b.tiles_per_slice = p.btiles_per_slice; b.slices = p.bslices; b.bl = bl;
+    const Sweep bound = pick_sweep<KS>(0, p, pipe);
+    if (!bound.kernel) return PS_EINVAL;
+    hipLaunchKernelGGL(bound.kernel, dim3((unsigned)(p.nqb * p.bslices)), dim3(512), bound.lds, st, b);
     PS_CHECK_LAUNCH();
     int64_t gs = ps_cdiv(nq, 4);
     if (gs > 4096) gs = 4096;
@@ -1262,21 +1263,8 @@ int launch_passes(const Plan &p, HArgs a, hipStream_t st, int32_t *thr0, int32_t
     // collect
     a.tile_begin = 0; a.tile_end = p.tiles; a.tiles_per_slice = p.tiles_per_slice; a.slices = p.slices; a.thr0 = thr0;
     a.list_base = 0;
-    const unsigned gc = (unsigned)(p.nqb * p.slices);
-    bool collected = false;
-    if constexpr (PipeServed<KS>::value) {
-        if (!p.db && pipe) {
-            hipLaunchKernelGGL((hamming_pipe_kernel<KS, 1>), dim3(gc), dim3(512), (size_t)PipeRing<KS>::value * KS * 1024 + (size_t)WAVES * p.cap * 64 * sizeof(uint32_t), st, a);
-            collected = true;
-        }
-    }
-    if constexpr (KS >= 4) {
-        if (!collected && !p.db) {
-            hipLaunchKernelGGL((hamming_mfma_kernel<KS, 1, 4, false>), dim3(gc), dim3(512), lds, st, a);
-            collected = true;
-        }
-    }
-    if (!collected) hipLaunchKernelGGL((hamming_mfma_kernel<KS, 1, 4, true>), dim3(gc), dim3(512), lds, st, a);
+    const Sweep collect = pick_sweep<KS>(1, p, pipe);
+    hipLaunchKernelGGL(collect.kernel, dim3((unsigned)(p.nqb * p.slices)), dim3(512), collect.lds, st, a);
     PS_CHECK_LAUNCH();
     return PS_OK;
 }
@@ -1285,7 +1273,7 @@ int launch_passes(const Plan &p, HArgs a, hipStream_t st, int32_t *thr0, int32_t
 
 extern "C" size_t ps_lsh_planes_bytes(int64_t n, int cs) {
     if (n <= 0 || cs <= 0 || cs % 8 != 0) return 0;
-    return (size_t)(((n + 31) / 32 + PAD_TILES - 1) / PAD_TILES * PAD_TILES) * (size_t)(cs / 8) * 1024;   // whole ring entries
+    return (size_t)plane_pieces(n, cs / 8) * 16;
 }
 
 extern "C" int ps_lsh_expand(const uint8_t *codes, int64_t n, int cs, void *planes, ps_stream_t stream) {
@@ -1294,14 +1282,7 @@ extern "C" int ps_lsh_expand(const uint8_t *codes, int64_t n, int cs, void *plan
     if (n == 0) return PS_OK;
     if (!codes || !planes || reinterpret_cast<size_t>(codes) % 4 != 0 || reinterpret_cast<size_t>(planes) % 16 != 0)
         return PS_EINVAL;
-    const int KS = cs / 8;
-    const int64_t pieces = (((n + 31) / 32 + PAD_TILES - 1) / PAD_TILES * PAD_TILES) * KS * 64;   // padding tiles are zero-filled
-    int64_t grid = ps_cdiv(pieces, 256);
-    if (grid > 256 * 64) grid = 256 * 64;
-    hipLaunchKernelGGL(lsh_expand_kernel, dim3((unsigned)grid), dim3(256), 0, ps_stream(stream),
-                       reinterpret_cast<const uint32_t *>(codes), n, KS, pieces, reinterpret_cast<uint4 *>(planes));
-    PS_CHECK_LAUNCH();
-    return PS_OK;
+    return launch_expand(reinterpret_cast<const uint32_t *>(codes), n, cs / 8, planes, ps_stream(stream));
 }
 
 extern "C" size_t ps_hamming_topk_mfma_workspace_bytes(int64_t nq, int64_t N, int cs, int k) {

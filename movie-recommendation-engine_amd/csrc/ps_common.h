@@ -87,3 +87,19 @@ __device__ __forceinline__ float ps_wave_sum_f32(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 #undef PS_DPP_MOV
+// Wave-wide minimum of 64-bit keys, result in every lane: the same six DPP steps on both halves of the key (a lane that a step
+// does not reach reads all ones and so keeps its own value), then lane 63
+__device__ __forceinline__ uint64_t ps_wave_min_u64(uint64_t v) {
+#define PS_STEP(ctrl, rows)                                                                                     \
+    {                                                                                                           \
+        const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)(uint32_t)v, ctrl, rows, 0xf, false); \
+        const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)(uint32_t)(v >> 32), ctrl, rows, 0xf, false); \
+        const uint64_t o = ((uint64_t)hi << 32) | lo;                                                           \
+        v = o < v ? o : v;                                                                                      \
+    }
+    PS_STEP(0xB1, 0xf) PS_STEP(0x4E, 0xf) PS_STEP(0x141, 0xf) PS_STEP(0x140, 0xf) PS_STEP(0x142, 0xa) PS_STEP(0x143, 0xc)
+#undef PS_STEP
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63);
+    return ((uint64_t)hi << 32) | lo;
+}

@@ -92,17 +92,24 @@ def test_mfma_scan_matches_oracle_and_popcount(cs, kind, N, nq, k):
         assert torch.equal(dmm, dm) and torch.equal(imm, im)
 
 
-@pytest.mark.parametrize("cs,k", [(32, 11), (64, 11), (64, 5), (32, 12), (16, 11), (64, 20)])
-def test_columns_that_fill_up_during_the_sweep(cs, k):
+@pytest.mark.parametrize("cs,k,pipe", [
+    pytest.param(32, 11, "1", id="32-11"), pytest.param(64, 11, "1", id="64-11"), pytest.param(64, 5, "1", id="64-5"),
+    pytest.param(32, 12, "1", id="32-12"), pytest.param(16, 11, "1", id="16-11"), pytest.param(64, 20, "1", id="64-20"),
+    # PS_HAMMING_PIPE=0: the same columns in the older two-workgroups-per-CU kernel (256- / 512-bit codes, k <= 12)
+    (32, 11, "0"), (64, 11, "0"), (64, 5, "0"), (32, 12, "0"),
+])
+def test_columns_that_fill_up_during_the_sweep(cs, k, pipe, monkeypatch):
     """The lane-private candidate columns hold k + 16 keys.  Random data never fills one (a lane sees ~3 candidates per
     sweep), so the in-sweep compaction -- bisection for the k-th smallest distance, keep everything up to it, tighten the
     lane's threshold; the serial exact selection when ties fill the column -- needs data built for it: a table whose first
     fifth is far from the queries (loose bound from the sample) and whose rest holds, for a few queries, long runs of
     near-duplicates (a) at pairwise different distances, (b) all at the same distance (ties by id), (c) packed into single
     tiles (many passing rows of one lane in one tile: the walk path with a column that is already nearly full).  Every
-    list must equal the popcount kernel's and the C oracle's."""
+    list must equal the popcount kernel's and the C oracle's.  pipe = "0" (PS_HAMMING_PIPE=0) sends the shapes that the
+    pipelined kernel serves through its predecessor, whose columns of the same size compact by the serial selection alone."""
     from oracle import c_oracle as co
     from pinsage_hip import dense
+    monkeypatch.setenv("PS_HAMMING_PIPE", pipe)
     rs = np.random.RandomState(cs * 100 + k)
     N, nq, nbits = 16384, 96, cs * 8
     codes = rs.randint(0, 256, size=(N, cs)).astype(np.uint8)
