@@ -235,12 +235,29 @@ int ps_linear(const float *x, int64_t M, int K, const float *W, int ldw, const f
  * +0.0); the pooled rows are never written as a matrix.  Served: N == 256, flags PS_RELU | PS_L2NORM (PS_WPERM allowed),
  * M >= 24 576, T <= 16, 16-byte aligned operands with K % 32 == 0 and H % 32 == 0; any other call returns PS_EUNSUPPORTED
  * without doing anything, and so does every call under the environment switch PS_GCN_FUSED=0 -- the caller then runs the pair.
- * workspace: ps_gcn_layer_workspace_bytes(M, H) bytes, 16-byte aligned, not preserved between calls. */
+ * workspace: ps_gcn_layer_workspace_bytes(M, H) bytes, 16-byte aligned, not preserved between calls.
+ * Two launches: the row order (below), then the GEMM over 64-row tiles in that order. */
 size_t ps_gcn_layer_workspace_bytes(int64_t M, int H);
 int ps_gcn_layer(const float *x, int64_t M, int K, const float *W, int ldw, const float *b, int N, const float *h_full,
                  int64_t n_full, int H, const int32_t *ids, const int32_t *counts, const float *wts, const int32_t *nvalid,
                  int T, int64_t max_idx, int renorm, const float *W2, int ldw2, int flags, float *y, void *workspace,
                  size_t workspace_bytes, ps_stream_t stream);
+/* The row order ps_gcn_layer runs its tiles in, for `layers` layers in one launch: ids int32[layers, M, T], nvalid int32[layers, M]
+ * (any M >= 0, T <= 16 as in ps_gcn_layer: PS_EUNSUPPORTED otherwise).  Per layer and per chunk of 2048 consecutive rows, ord_out[2048 c ..] holds the chunk's rows that keep a neighbour
+ * (j < nvalid[i], 0 <= ids[i, j] <= max_idx) in ascending order, then its other rows in ascending order; ord_out is
+ * int32[layers, 64 * ceil(M / 64)], the entries from M on are -1.  tile_heavy_out int32[layers, ceil(M / 64)]: 1 where
+ * ord_out[64 t .. 64 t + 63] holds a row that keeps a neighbour, else 0.  No atomics: the same output on every run.  max_idx is
+ * taken as given: pass min(max_idx, n_full - 1) of the layer call.
+ * ps_gcn_layer_ordered is ps_gcn_layer (same arguments, gates, workspace and results, bit for bit) with the order of its layer
+ * supplied by the caller -- ord / tile_heavy: one layer's rows of the two buffers -- and is the GEMM launch alone.  The order
+ * depends on the sampler's output only, so a model makes it once per step for all its layers, before the first GEMM. */
+int ps_gcn_order(const int32_t *ids, const int32_t *nvalid, int layers, int64_t M, int T, int64_t max_idx, int32_t *ord_out,
+                 int32_t *tile_heavy_out, ps_stream_t stream);
+int ps_gcn_layer_ordered(const float *x, int64_t M, int K, const float *W, int ldw, const float *b, int N, const float *h_full,
+                         int64_t n_full, int H, const int32_t *ids, const int32_t *counts, const float *wts,
+                         const int32_t *nvalid, int T, int64_t max_idx, int renorm, const float *W2, int ldw2, int flags, float *y,
+                         void *workspace, size_t workspace_bytes, const int32_t *ord, const int32_t *tile_heavy,
+                         ps_stream_t stream);
 
 /* ---- a10: LSHIndex.build/search (utils/nearest_neighbors.py:28-68 -> faiss.IndexLSH) ---------
  * codes[n, nbits/8] : bit j = ( x . A[j,:] >= 0 ), LSB-first (faiss fvec2bitvec); A float[nbits,D].

@@ -62,9 +62,9 @@ struct GemmArgs {
     float *y;            // EPI 0
     uint8_t *codes; int cs;  // EPI 1
     const int64_t *grp;      // optional (grouped products, psi_linear_grouped): per 64-row block (W row offset, columns, y offset)
-    // ps_gcn_layer (gemm_f32_kernel<..., GCN = PAGES>): rows in class order, the count of rows that keep a neighbour, the pooled-row
-    // slabs (64 x H per tile), and the pooling's operands (csrc/pool_row.h)
-    const int32_t *ord; const int32_t *nheavy; float *slab;
+    // ps_gcn_layer (gemm_f32_kernel<..., GCN = PAGES>): rows in class order, per 64-row tile whether it holds a row that keeps a
+    // neighbour, the pooled-row slabs (64 x H per tile), and the pooling's operands (csrc/pool_row.h)
+    const int32_t *ord; const int32_t *tile_heavy; float *slab;
     const float *hf; int H; const int32_t *ids; const int32_t *counts; const float *wts; const int32_t *nvalid; int T; int renorm;
     int64_t max_idx;
     // EPI 2 (ps_rank_count): per row the target's similarity and id, the id of column 0, the counts (+=)
@@ -72,6 +72,22 @@ struct GemmArgs {
     // EPI 3 (ps_hardest_negative): per row the largest ps_best_pack(similarity, column) (max=); xdiag: column == row is no candidate
     unsigned long long *best; int xdiag;
 };
+
+// ps_gcn_layer: rows per workgroup of gcn_order_kernel (below, at the entry), which sorts each chunk of rows on its own
+constexpr int GCN_CHUNK = 2048;
+// ... and the tile block b of the layer GEMM runs.  Every chunk holds its heavy tiles first, so the blocks visit the tiles round by
+// round -- tile 0 of every chunk, then tile 1 of every chunk, ... -- and the heavy tiles of the whole layer are the first blocks,
+// as one class order over all rows had them.  With block b on tile b the blocks that share a CU, a multiple of 256 apart, stand
+// at the same place of their chunks (256 is a multiple of a chunk's 32 tiles), i.e. heavy tiles meet heavy tiles on one CU: the
+// benchmark's layer of 923 tiles measured 179 us instead of 128.
+// The partial last chunk (`tail` tiles) takes part in the first `tail` rounds; the short last tile stays the last tile index.
+__device__ __forceinline__ uint32_t gcn_block_tile(uint32_t b, uint32_t ntiles) {
+    constexpr uint32_t CT = GCN_CHUNK / 64;
+    const uint32_t nfull = ntiles / CT, tail = ntiles - nfull * CT, head = tail * (nfull + 1);
+    if (b < head) return (b % (nfull + 1)) * CT + b / (nfull + 1);
+    b -= head;
+    return (b % nfull) * CT + tail + b / nfull;
+}
 
 // 8 consecutive k of one row (zero-filled outside [0,K) / invalid row)
 __device__ __forceinline__ void load8(const float *base, bool row_ok, int k, int K, bool vec_ok, float (&v)[8]) {
@@ -449,7 +465,7 @@ __global__ __launch_bounds__(WM * WN * 64, PS_GEMM_OCC) void gemm_f32_kernel(Gem
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int wm = wv / WN, wn = wv % WN;
-    const int64_t m0 = (int64_t)blockIdx.x * BM;
+    const int64_t m0 = (int64_t)(GCN > 0 ? gcn_block_tile(blockIdx.x, (uint32_t)((g.M + BM - 1) / BM)) : blockIdx.x) * BM;
     const int n0 = blockIdx.y * BN;
     const int li = lane & 31, lh = lane >> 5;
     // grouped products (the inverted-file scan, csrc/dot_topk.hip): row block blockIdx.x multiplies its 64 rows of x with ITS
@@ -471,14 +487,15 @@ __global__ __launch_bounds__(WM * WN * 64, PS_GEMM_OCC) void gemm_f32_kernel(Gem
     int trace_step = 0;
 #endif
     PS_TRACE(0);
-    // ps_gcn_layer: tile t holds rows ord[64 t .. 64 t + 63] (rows that keep a neighbour first).  A tile that holds one of them
-    // ("heavy") pools its 64 rows into its slab and contracts K + K2; any other tile contracts K only -- its pooled rows are +0.0, and
-    // fmaf(+0.0, w, acc) == acc for finite w except acc == -0.0, which the ReLU of the epilogue maps to +0.0 either way
+    // ps_gcn_layer: tile t holds rows ord[64 t .. 64 t + 63] (in each chunk the rows that keep a neighbour first).  A tile that holds
+    // one of them ("heavy", tile_heavy[t]) pools its 64 rows into its slab and contracts K + K2; any other tile contracts K only --
+    // its pooled rows are +0.0, and fmaf(+0.0, w, acc) == acc for finite w except acc == -0.0, which the ReLU of the epilogue maps
+    // to +0.0 either way
     int64_t xrow[A_ITEMS];
     (void)xrow;
     if constexpr (GCN > 0) {
         static_assert(FAST && EPI == 0 && BM == 64 && NT == 256, "the 64-row tile of the layer GEMM");
-        const bool heavy = m0 < (int64_t)*g.nheavy;                              // block-uniform
+        const bool heavy = g.tile_heavy[m0 / BM] != 0;                           // block-uniform
         if (tid < BM) sOrd[tid] = g.ord[m0 + tid < g.M ? m0 + tid : g.M - 1];
         if (heavy) {
             float *slab = g.slab + (int64_t)blockIdx.x * BM * g.H;
@@ -1366,91 +1383,107 @@ extern "C" int ps_linear(const float *x, int64_t M, int K, const float *W, int l
 }
 
 // ---- ps_gcn_layer ---------------------------------------------------------------------------------------------------------
-// One GraphSAGE layer, y = l2norm(relu(x W^T + pool(h_full) W2^T + b)), as three launches: gcn_count_kernel and gcn_order_kernel
-// sort the rows into two classes -- rows that keep at least one neighbour ("heavy") first, then the rest, each class in ascending
-// row order (a stable partition: per chunk a count, then per chunk the prefix of the counts and a block scan; no atomics, so the
-// order is the same on every run) -- and gemm_f32_kernel<1, 4, 2, 2, 32, 0, true, PAGES> runs the 64 x 256 tiles over the rows in
-// that order: a heavy tile pools its 64 rows (pool4_row, the same function as ps_importance_pool) into its slab of the workspace,
-// which stays in L2, and contracts K + K2; a tile of rows that keep nothing contracts K only.  The count of heavy rows stays on the
-// device.  At T = 10 on the catalogue graphs about half of the rows keep no item neighbour.
+// One GraphSAGE layer, y = l2norm(relu(x W^T + pool(h_full) W2^T + b)), as two launches: gcn_order_kernel sorts the rows of every
+// 2048-row chunk into two classes -- rows that keep at least one neighbour ("heavy") first, then the rest, each class in ascending
+// row order -- and flags the 64-row tiles that hold a heavy row; gemm_f32_kernel<1, 4, 2, 2, 32, 0, true, PAGES> runs the 64 x 256
+// tiles over the rows in that order: a flagged tile pools its 64 rows (pool4_row, the same function as ps_importance_pool) into its
+// slab of the workspace, which stays in L2, and contracts K + K2; a tile of rows that keep nothing contracts K only.  The order
+// depends on the sampler's output alone: ps_gcn_order makes it for all layers of a step in ONE launch, before the first GEMM, and
+// ps_gcn_layer_ordered is then the GEMM alone.  At T = 10 on the catalogue graphs about half of the rows keep no item neighbour
+// (DESIGN.md 4).
 namespace {
 
-constexpr int GCN_MAX_CHUNKS = 1024;
-
-int64_t gcn_chunk_rows(int64_t M) {
-    const int64_t c = ps_cdiv(ps_cdiv(M, GCN_MAX_CHUNKS), 256) * 256;
-    return c > 256 ? c : 256;
-}
+// GCN_CHUNK rows per workgroup of gcn_order_kernel: a multiple of 64, so no tile straddles two chunks, and nothing is shared between chunks:
+// no count pass, no atomics, the same output on every run.  The price is one tile per chunk that holds both classes and runs as
+// heavy (exact: its empty rows pool to +0.0, see gemm_f32_kernel): at most M / 2048 tiles out of M / 64.  512 threads x 4 passes:
+// all of a thread's entries (4 x 17 words) are in flight at once without spilling; 4096 rows per chunk did not fit that way
+// (1024 threads leave 128 registers, 8 passes of 512 threads need more than 256).
+constexpr int GCN_NT = 512;
+constexpr int GCN_PASSES = GCN_CHUNK / GCN_NT;
+constexpr int GCN_GROUPS = GCN_CHUNK / 64;         // 64-row groups of a chunk = (pass, wave) pairs in row order = tiles of the chunk
+static_assert(GCN_CHUNK % GCN_NT == 0 && GCN_NT % 64 == 0 && GCN_GROUPS <= 64, "one lane of wave 0 per 64-row group");
 
 struct GcnWorkspace {
-    size_t slab, ord, cnt, total;
+    size_t slab, ord, flag, total;
 };
 GcnWorkspace gcn_workspace(int64_t M, int H) {
     GcnWorkspace w;
     w.slab = 0;
     w.ord = (size_t)ps_cdiv(M, 64) * 64 * (size_t)H * sizeof(float);
-    w.cnt = w.ord + (size_t)ps_cdiv(M, 64) * 64 * sizeof(int32_t);
-    w.total = w.cnt + (GCN_MAX_CHUNKS + 64) * sizeof(int32_t);      // chunk counts, then the heavy-row count
+    w.flag = w.ord + (size_t)ps_cdiv(M, 64) * 64 * sizeof(int32_t);
+    w.total = w.flag + ((size_t)ps_cdiv(M, 64) * sizeof(int32_t) + 255) / 256 * 256;      // one flag per tile
     return w;
 }
 
-__global__ __launch_bounds__(256) void gcn_count_kernel(const int32_t *__restrict__ ids, const int32_t *__restrict__ nvalid, int64_t M,
-                                                        int T, int64_t max_idx, int64_t chunk, int32_t *__restrict__ cnt) {
-    __shared__ int sw[4];
+// grid (chunks, layers); ids [layers, M, T], nvalid [layers, M]; ord [layers, ord_stride], tile_heavy [layers, ntiles].
+// Chunk c of a layer: ord[2048 c ..] = its heavy rows ascending, then its other rows ascending (a stable partition);
+// tile_heavy[32 c + e] = (64 e < heavy rows of the chunk), i.e. tile 32 c + e holds a heavy row.  ord[M .. ord_stride) = -1.
+__global__ __launch_bounds__(GCN_NT) void gcn_order_kernel(const int32_t *__restrict__ ids, const int32_t *__restrict__ nvalid, int64_t M,
+                                                           int T, int64_t max_idx, int32_t *__restrict__ ord, int64_t ord_stride,
+                                                           int32_t *__restrict__ tile_heavy, int64_t ntiles) {
+    __shared__ int sh[GCN_GROUPS + 1];                       // heavy rows per 64-row group; then their exclusive prefix and the total
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int64_t r0 = (int64_t)blockIdx.x * chunk, r1 = r0 + chunk < M ? r0 + chunk : M;
-    int c = 0;
-    for (int64_t i = r0 + tid; i < r1; i += 256) c += pool_row_keeps(ids, nvalid, i, T, max_idx) ? 1 : 0;
-    c = ps_wave_sum_i32(c);
-    if (lane == 0) sw[wv] = c;
-    __syncthreads();
-    if (tid == 0) cnt[blockIdx.x] = sw[0] + sw[1] + sw[2] + sw[3];
-}
-
-__global__ __launch_bounds__(256) void gcn_order_kernel(const int32_t *__restrict__ ids, const int32_t *__restrict__ nvalid, int64_t M,
-                                                        int T, int64_t max_idx, int64_t chunk, int nchunks,
-                                                        const int32_t *__restrict__ cnt, int32_t *__restrict__ ord,
-                                                        int32_t *__restrict__ nheavy) {
-    __shared__ int sb[4], st[4], sh[4], se[4];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int64_t r0 = (int64_t)blockIdx.x * chunk, r1 = r0 + chunk < M ? r0 + chunk : M;
-    // heavy rows of the chunks before this one, and of all chunks
-    int before = 0, total = 0;
-    for (int j = tid; j < nchunks; j += 256) {
-        const int v = cnt[j];
-        total += v;
-        before += j < (int)blockIdx.x ? v : 0;
+    const int64_t layer = blockIdx.y;
+    ids += layer * M * T;
+    nvalid += layer * M;
+    ord += layer * ord_stride;
+    tile_heavy += layer * ntiles;
+    const int64_t r0 = (int64_t)blockIdx.x * GCN_CHUNK;
+    const int rows = (int)(M - r0 < GCN_CHUNK ? M - r0 : GCN_CHUNK);         // >= 1: the grid has cdiv(M, GCN_CHUNK) chunks
+    // f[p]: does row p * GCN_NT + tid of the chunk keep a neighbour (the test of pool_row_keeps, T <= 16)?  The entries of all
+    // passes are requested before the first one is looked at -- no branch per lane: a row that does not exist reads the chunk's
+    // last one and is masked afterwards -- which is one round trip to memory instead of two per pass
+    int k[GCN_PASSES];
+    int32_t v[GCN_PASSES][16];
+#pragma unroll
+    for (int p = 0; p < GCN_PASSES; ++p) {
+        const int l = p * GCN_NT + tid;
+        const int64_t i = r0 + (l < rows ? l : rows - 1);
+        k[p] = nvalid[i];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) v[p][u] = u < T ? ids[i * T + u] : -1;                      // u < T: scalar
     }
-    before = ps_wave_sum_i32(before);
-    total = ps_wave_sum_i32(total);
-    if (lane == 0) { sb[wv] = before; st[wv] = total; }
+    bool f[GCN_PASSES];
+#pragma unroll
+    for (int p = 0; p < GCN_PASSES; ++p) {
+        const int kk = p * GCN_NT + tid < rows ? (k[p] < T ? k[p] : T) : 0;
+        bool keep = false;
+#pragma unroll
+        for (int u = 0; u < 16; ++u) keep |= u < kk && v[p][u] >= 0 && (int64_t)v[p][u] <= max_idx;
+        f[p] = keep;
+    }
+#pragma unroll
+    for (int p = 0; p < GCN_PASSES; ++p) {
+        const uint64_t hm = __ballot(f[p]);
+        if (lane == 0) sh[p * (GCN_NT / 64) + wv] = __popcll(hm);
+    }
     __syncthreads();
-    before = sb[0] + sb[1] + sb[2] + sb[3];
-    total = st[0] + st[1] + st[2] + st[3];
-    if (blockIdx.x == 0 && tid == 0) *nheavy = total;
-    int64_t hoff = before, eoff = total + (r0 - before);     // next slot of each class
-    for (int64_t base = r0; base < r1; base += 256) {
-        const int64_t i = base + tid;
-        const bool in = i < r1;
-        const bool f = in && pool_row_keeps(ids, nvalid, i, T, max_idx);
-        const uint64_t hm = __ballot(f), em = __ballot(in && !f);
+    if (wv == 0) {                                           // exclusive prefix over the groups, in row order
+        const int c = lane < GCN_GROUPS ? sh[lane] : 0;
+        int incl = c;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int up = __shfl_up(incl, d, 64);
+            incl += lane >= d ? up : 0;
+        }
+        if (lane < GCN_GROUPS) sh[lane] = incl - c;
+        if (lane == 63) sh[GCN_GROUPS] = incl;
+    }
+    __syncthreads();
+    const int nh = sh[GCN_GROUPS];
+#pragma unroll
+    for (int p = 0; p < GCN_PASSES; ++p) {
+        const int grp = p * (GCN_NT / 64) + wv, l = grp * 64 + lane;
+        const bool in = l < rows;
+        const uint64_t hm = __ballot(f[p]), em = __ballot(in && !f[p]);
         const int hr = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(hm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hm, 0u));
         const int er = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(em >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)em, 0u));
-        if (lane == 0) { sh[wv] = __popcll(hm); se[wv] = __popcll(em); }
-        __syncthreads();
-        int hb = 0, eb = 0, ht = 0, et = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            hb += w < wv ? sh[w] : 0;
-            eb += w < wv ? se[w] : 0;
-            ht += sh[w];
-            et += se[w];
-        }
-        if (in) ord[f ? hoff + hb + hr : eoff + eb + er] = (int32_t)i;
-        hoff += ht;
-        eoff += et;
-        __syncthreads();                                     // sh / se are rewritten by the next pass
+        const int hb = sh[grp];                              // heavy rows of the chunk before this group
+        const int eb = (grp * 64 < rows ? grp * 64 : rows) - hb;
+        if (in) ord[r0 + (f[p] ? hb + hr : nh + eb + er)] = (int32_t)(r0 + l);
     }
+    if (tid < GCN_GROUPS && tid * 64 < rows) tile_heavy[r0 / 64 + tid] = tid * 64 < nh ? 1 : 0;
+    if (r0 + rows == M && M + tid < ord_stride) ord[M + tid] = -1;          // the last chunk pads the last tile (< 64 entries)
 }
 
 bool env_set(const char *name) {
@@ -1458,17 +1491,19 @@ bool env_set(const char *name) {
     return e != nullptr && *e != '\0';
 }
 
-}  // namespace
-
-extern "C" size_t ps_gcn_layer_workspace_bytes(int64_t M, int H) {
-    if (M <= 0 || H <= 0) return 0;
-    return gcn_workspace(M, H).total;
+int gcn_order_launch(const int32_t *ids, const int32_t *nvalid, int layers, int64_t M, int T, int64_t max_idx, int32_t *ord,
+                     int32_t *tile_heavy, hipStream_t st) {
+    const int64_t ntiles = ps_cdiv(M, 64);
+    hipLaunchKernelGGL(gcn_order_kernel, dim3((unsigned)ps_cdiv(M, GCN_CHUNK), (unsigned)layers), dim3(GCN_NT), 0, st, ids, nvalid, M, T,
+                       max_idx, ord, ntiles * 64, tile_heavy, ntiles);
+    PS_CHECK_LAUNCH();
+    return PS_OK;
 }
 
-extern "C" int ps_gcn_layer(const float *x, int64_t M, int K, const float *W, int ldw, const float *b, int N, const float *h_full,
-                            int64_t n_full, int H, const int32_t *ids, const int32_t *counts, const float *wts, const int32_t *nvalid,
-                            int T, int64_t max_idx, int renorm, const float *W2, int ldw2, int flags, float *y, void *workspace,
-                            size_t workspace_bytes, ps_stream_t stream) {
+// the argument checks and shape gates of ps_gcn_layer / ps_gcn_layer_ordered
+int gcn_layer_check(const float *x, int64_t M, int K, const float *W, int ldw, int N, const float *h_full, int64_t n_full, int H,
+                    const int32_t *ids, const int32_t *counts, const float *wts, const int32_t *nvalid, int T, const float *W2, int ldw2,
+                    int flags, const float *y, const void *workspace, size_t workspace_bytes) {
     if (M < 0 || K <= 0 || N <= 0 || ldw < K || H <= 0 || ldw2 < H || T <= 0 || n_full < 0) return PS_EINVAL;
     if (flags & ~(PS_RELU | PS_L2NORM | PS_WPERM)) return PS_EINVAL;
     if (M > 0 && (!x || !W || !y || !h_full || !W2 || !ids || !nvalid || (!counts && !wts))) return PS_EINVAL;
@@ -1483,26 +1518,58 @@ extern "C" int ps_gcn_layer(const float *x, int64_t M, int K, const float *W, in
         return PS_EUNSUPPORTED;
     if (!aligned_operand(x, K, K) || !aligned_operand(W, K, ldw) || !aligned_operand(W2, H, ldw2) || !aligned_operand(h_full, H, H))
         return PS_EUNSUPPORTED;
-    const GcnWorkspace wl = gcn_workspace(M, H);
-    if (!workspace || workspace_bytes < wl.total || reinterpret_cast<size_t>(workspace) % 16 != 0) return PS_EWORKSPACE;
+    if (!workspace || workspace_bytes < gcn_workspace(M, H).total || reinterpret_cast<size_t>(workspace) % 16 != 0) return PS_EWORKSPACE;
+    return PS_OK;
+}
+
+}  // namespace
+
+extern "C" size_t ps_gcn_layer_workspace_bytes(int64_t M, int H) {
+    if (M <= 0 || H <= 0) return 0;
+    return gcn_workspace(M, H).total;
+}
+
+extern "C" int ps_gcn_order(const int32_t *ids, const int32_t *nvalid, int layers, int64_t M, int T, int64_t max_idx, int32_t *ord_out,
+                            int32_t *tile_heavy_out, ps_stream_t stream) {
+    if (layers < 0 || layers > 65535 || M < 0 || M > 0x7fffffff - 64 || T <= 0) return PS_EINVAL;
+    if (T > 16) return PS_EUNSUPPORTED;                  // the gate of the layer GEMM that reads the order
+    if (layers == 0 || M == 0) return PS_OK;
+    if (!ids || !nvalid || !ord_out || !tile_heavy_out) return PS_EINVAL;
+    return gcn_order_launch(ids, nvalid, layers, M, T, max_idx, ord_out, tile_heavy_out, ps_stream(stream));
+}
+
+extern "C" int ps_gcn_layer_ordered(const float *x, int64_t M, int K, const float *W, int ldw, const float *b, int N, const float *h_full,
+                                    int64_t n_full, int H, const int32_t *ids, const int32_t *counts, const float *wts,
+                                    const int32_t *nvalid, int T, int64_t max_idx, int renorm, const float *W2, int ldw2, int flags,
+                                    float *y, void *workspace, size_t workspace_bytes, const int32_t *ord, const int32_t *tile_heavy,
+                                    ps_stream_t stream) {
+    const int rc = gcn_layer_check(x, M, K, W, ldw, N, h_full, n_full, H, ids, counts, wts, nvalid, T, W2, ldw2, flags, y, workspace,
+                                   workspace_bytes);
+    if (rc != PS_OK) return rc;
+    if (!ord || !tile_heavy) return PS_EINVAL;
     if (max_idx > n_full - 1) max_idx = n_full - 1;
-    unsigned char *ws = static_cast<unsigned char *>(workspace);
-    int32_t *ord = reinterpret_cast<int32_t *>(ws + wl.ord), *cnt = reinterpret_cast<int32_t *>(ws + wl.cnt);
-    int32_t *nheavy = cnt + GCN_MAX_CHUNKS;
-    hipStream_t st = ps_stream(stream);
-    const int64_t chunk = gcn_chunk_rows(M);
-    const int nchunks = (int)ps_cdiv(M, chunk);
-    hipLaunchKernelGGL(gcn_count_kernel, dim3((unsigned)nchunks), dim3(256), 0, st, ids, nvalid, M, T, max_idx, chunk, cnt);
-    PS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gcn_order_kernel, dim3((unsigned)nchunks), dim3(256), 0, st, ids, nvalid, M, T, max_idx, chunk, nchunks, cnt, ord,
-                       nheavy);
-    PS_CHECK_LAUNCH();
     GemmArgs g{x, M, K, W, ldw, nullptr, H, W2, ldw2, b, N, flags, y, nullptr, 0, nullptr,
-               ord, nheavy, reinterpret_cast<float *>(ws + wl.slab), h_full, H, ids, counts, wts, nvalid, T, renorm, max_idx};
+               ord, tile_heavy, static_cast<float *>(workspace), h_full, H, ids, counts, wts, nvalid, T, renorm, max_idx};
     const dim3 grid((unsigned)ps_cdiv(M, 64), 1);
-    hipLaunchKernelGGL((gemm_f32_kernel<1, 4, 2, 2, 32, 0, true, 1>), grid, dim3(256), 0, st, g);
+    hipLaunchKernelGGL((gemm_f32_kernel<1, 4, 2, 2, 32, 0, true, 1>), grid, dim3(256), 0, ps_stream(stream), g);
     PS_CHECK_LAUNCH();
     return PS_OK;
+}
+
+extern "C" int ps_gcn_layer(const float *x, int64_t M, int K, const float *W, int ldw, const float *b, int N, const float *h_full,
+                            int64_t n_full, int H, const int32_t *ids, const int32_t *counts, const float *wts, const int32_t *nvalid,
+                            int T, int64_t max_idx, int renorm, const float *W2, int ldw2, int flags, float *y, void *workspace,
+                            size_t workspace_bytes, ps_stream_t stream) {
+    int rc = gcn_layer_check(x, M, K, W, ldw, N, h_full, n_full, H, ids, counts, wts, nvalid, T, W2, ldw2, flags, y, workspace,
+                             workspace_bytes);
+    if (rc != PS_OK) return rc;
+    const GcnWorkspace wl = gcn_workspace(M, H);
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    int32_t *ord = reinterpret_cast<int32_t *>(ws + wl.ord), *tile_heavy = reinterpret_cast<int32_t *>(ws + wl.flag);
+    rc = gcn_order_launch(ids, nvalid, 1, M, T, max_idx > n_full - 1 ? n_full - 1 : max_idx, ord, tile_heavy, ps_stream(stream));
+    if (rc != PS_OK) return rc;
+    return ps_gcn_layer_ordered(x, M, K, W, ldw, b, N, h_full, n_full, H, ids, counts, wts, nvalid, T, max_idx, renorm, W2, ldw2, flags, y,
+                                workspace, workspace_bytes, ord, tile_heavy, stream);
 }
 
 // out[r][8 g + j] = W[r][8 g + p(j)], p = 0 2 4 6 1 3 5 7: the order in which the GEMM's LDS image holds an 8-k group

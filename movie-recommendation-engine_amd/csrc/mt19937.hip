@@ -566,11 +566,15 @@ constexpr int64_t HALF = CHUNK / 2;
 // wanted run (the whole-stream request): the hull [lo, hi) IS the wanted set (the general tests cost the 722-workgroup launch 6 us).
 template <bool RANGED>
 __global__ __launch_bounds__(256) void mt_chunk_kernel(const uint32_t *states, int nparts, int64_t c0, WinSet ws, Wanted wt, int64_t w_lo,
-                                                       uint32_t *raw, int64_t key_w, uint32_t *state_out, int pos, int32_t *pos_out) {
+                                                       uint32_t *raw, int64_t key_w, uint32_t *state_out, int pos, int32_t *pos_out,
+                                                       const uint32_t *word0) {
     __shared__ uint32_t mt[2][MT_N];
     const int t = threadIdx.x;
     const bool back = blockIdx.y != 0;
     if (blockIdx.x == 0 && !back && t == 0 && key_w >= 1) pos_out[0] = pos;
+    // stream word 0 is the word the state stands on, not a chunk word: the launch that opens the chain left it in word0, and
+    // the forward workgroup of slot 0 (always launched, whatever is wanted) stores it before it looks at its own words
+    if (blockIdx.x == 0 && !back && t == 0 && w_lo == 0) raw[0] = word0[0];
     const int64_t wbase = 1 + (c0 + (blockIdx.x == 0 ? 0 : win_of(ws, blockIdx.x - 1))) * CHUNK;
     // wanted words of this workgroup: the part of wt inside its half chunk [h_lo, h_hi); [lo, hi) = the hull of that part
     int64_t h_lo = back ? wbase - HALF : wbase, h_hi = back ? wbase : wbase + HALF;
@@ -983,17 +987,15 @@ static int mt_generate(const uint32_t *state_in, int pos_in, int64_t skip, int64
             PS_CHECK_LAUNCH();
         }
     }
-    // 4. chunks -> raw words; word 0 separately
+    // 4. chunks -> raw words (word 0, when kept, by slot 0's forward workgroup)
     const int64_t key_fold = p.key_w >= 1 ? p.key_w : -(int64_t)4 * MT_N;         // no stream word lies in the folded range then
     if (ranged)
         hipLaunchKernelGGL(mt_chunk_kernel<true>, dim3((unsigned)Kw, 2), dim3(256), 0, st, plain_states ? plainS : states, plain_states ? 1 : JP,
-                           p.c0, ws, wt, p.w_lo, raw, key_fold, state_out, p.pos_out, pos_out);
+                           p.c0, ws, wt, p.w_lo, raw, key_fold, state_out, p.pos_out, pos_out, word0);
     else
         hipLaunchKernelGGL(mt_chunk_kernel<false>, dim3((unsigned)Kw, 2), dim3(256), 0, st, plain_states ? plainS : states, plain_states ? 1 : JP,
-                           p.c0, ws, wt, p.w_lo, raw, key_fold, state_out, p.pos_out, pos_out);
+                           p.c0, ws, wt, p.w_lo, raw, key_fold, state_out, p.pos_out, pos_out, word0);
     PS_CHECK_LAUNCH();
-    if (p.w_lo == 0)
-        if (hipMemcpyAsync(raw, word0, 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return PS_ELAUNCH;
     // 5. doubles (raw mode: the consumer tempers and combines)
     if (n > 0 && !raw_out) {
         int64_t grid = ps_cdiv(n, 256);

@@ -90,11 +90,42 @@ def linear(x, W, b=None, x2=None, W2=None, relu=False, l2norm=False):
     return y
 
 
-def gcn_layer(x, W, b, h_full, ids, counts, nvalid, W2, wts=None, max_idx=None, renorm=True, relu=True, l2norm=True):
+GCN_MIN_ROWS, GCN_MAX_T = 64 * 384, 16      # the M / T gates of ps_gcn_layer: gcn_orders makes no order the layer call would refuse
+
+
+def gcn_orders(ids, nvalid, max_idx):
+    """The row orders of ps_gcn_layer for several layers in ONE launch (ps_gcn_order): ids / nvalid are lists of the layers'
+    [M, T] / [M] int32 tensors, max_idx the bound the layer calls will pass (at most h_full.size(0) - 1).  Returns one
+    (ord, tile_heavy) pair per layer for gcn_layer(order=...), or None where ps_gcn_layer does not serve the shape.  The slices
+    walk_sample_layers returns are passed as the one buffer they are; anything else is stacked first."""
+    _require_cuda(*ids, *nvalid)
+    layers, M, T = len(ids), ids[0].size(0), ids[0].size(1)
+    if layers == 0 or M < GCN_MIN_ROWS or T > GCN_MAX_T:
+        return None
+    if any(t.shape != (M, T) or t.dtype != torch.int32 for t in ids) or any(t.shape != (M,) or t.dtype != torch.int32 for t in nvalid):
+        raise ValueError("shape mismatch")
+
+    def one_buffer(ts):
+        step = ts[0].numel() * 4
+        if all(t.is_contiguous() and t.data_ptr() == ts[0].data_ptr() + r * step for r, t in enumerate(ts)):
+            return ts[0]                                 # consecutive slices: the first one's pointer is the buffer's
+        return torch.stack(ts)
+    ids_all, nv_all = one_buffer(ids), one_buffer(nvalid)
+    dev = ids[0].device
+    ntiles = (M + 63) // 64
+    ord_ = torch.empty((layers, ntiles * 64), dtype=torch.int32, device=dev)
+    heavy = torch.empty((layers, ntiles), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        nv.call("ps_gcn_order", nv.ptr(ids_all), nv.ptr(nv_all), layers, M, T, int(max_idx), nv.ptr(ord_), nv.ptr(heavy), nv.stream())
+    return [(ord_[r], heavy[r]) for r in range(layers)]
+
+
+def gcn_layer(x, W, b, h_full, ids, counts, nvalid, W2, wts=None, max_idx=None, renorm=True, relu=True, l2norm=True, order=None):
     """linear(x, W, b, x2=importance_pool(h_full, ids, counts, wts, nvalid, max_idx, renorm), W2=W2, relu, l2norm) -- the same
-    bits -- in one launch where ps_gcn_layer serves the shape (rows that keep no neighbour skip the W2 half, the pooled rows are
-    not written out); elsewhere, and under PS_GCN_FUSED=0, as that pair of calls.  W / W2: matrices or StagedWeights (both or
-    neither)."""
+    bits -- in two launches (row order, GEMM) where ps_gcn_layer serves the shape (rows that keep no neighbour skip the W2 half,
+    the pooled rows are not written out); elsewhere, and under PS_GCN_FUSED=0, as that pair of calls.  W / W2: matrices or
+    StagedWeights (both or neither).  order: this layer's (ord, tile_heavy) of gcn_orders, made from the same ids / nvalid /
+    max_idx -- the call is then the GEMM launch alone (ps_gcn_layer_ordered)."""
     from . import sampling
     staged = isinstance(W, StagedWeight)
     if isinstance(W2, StagedWeight) != staged:
@@ -122,10 +153,21 @@ def gcn_layer(x, W, b, h_full, ids, counts, nvalid, W2, wts=None, max_idx=None, 
     ws, wsb = nv.workspace("ps_gcn_layer_workspace_bytes", x.device, M, H)
     if wsb > 0:
         y = torch.empty((M, N), dtype=torch.float32, device=x.device)
+        if order is not None:
+            ord_, heavy = order
+            if ord_.dtype != torch.int32 or heavy.dtype != torch.int32 or ord_.numel() != (M + 63) // 64 * 64 \
+                    or heavy.numel() != (M + 63) // 64:
+                raise ValueError("order: (int32[64 * ceil(M / 64)], int32[ceil(M / 64)]) of gcn_orders expected")
         with torch.cuda.device(x.device):
-            rc = nv.lib().ps_gcn_layer(nv.ptr(x), M, K, nv.ptr(Wk, contiguous=False), ldw, nv.ptr(b), N, nv.ptr(h_full), n_full, H,
-                                       nv.ptr(ids), nv.ptr(counts), nv.ptr(wts), nv.ptr(nvalid), T, int(max_idx), int(renorm),
-                                       nv.ptr(W2k, contiguous=False), ldw2, flags, nv.ptr(y), nv.ptr(ws), wsb, nv.stream())
+            if order is not None:
+                rc = nv.lib().ps_gcn_layer_ordered(nv.ptr(x), M, K, nv.ptr(Wk, contiguous=False), ldw, nv.ptr(b), N, nv.ptr(h_full),
+                                                   n_full, H, nv.ptr(ids), nv.ptr(counts), nv.ptr(wts), nv.ptr(nvalid), T, int(max_idx),
+                                                   int(renorm), nv.ptr(W2k, contiguous=False), ldw2, flags, nv.ptr(y), nv.ptr(ws), wsb,
+                                                   nv.ptr(ord_), nv.ptr(heavy), nv.stream())
+            else:
+                rc = nv.lib().ps_gcn_layer(nv.ptr(x), M, K, nv.ptr(Wk, contiguous=False), ldw, nv.ptr(b), N, nv.ptr(h_full), n_full, H,
+                                           nv.ptr(ids), nv.ptr(counts), nv.ptr(wts), nv.ptr(nvalid), T, int(max_idx), int(renorm),
+                                           nv.ptr(W2k, contiguous=False), ldw2, flags, nv.ptr(y), nv.ptr(ws), wsb, nv.stream())
         if rc != nv.PS_EUNSUPPORTED:
             nv.check(rc, "ps_gcn_layer")
             return y
@@ -437,6 +479,14 @@ def _window_polys(dev):
 
 
 _pending_state = []
+_handback_host = {}          # device -> pinned int32[625]: the state's 624 words, then pos (one hand-back in flight at most)
+
+
+def _handback_buffer(dev):
+    key = str(dev)
+    if key not in _handback_host:
+        _handback_host[key] = torch.empty(625, dtype=torch.int32).pin_memory()
+    return _handback_host[key]
 
 
 def finish_rng_state():
@@ -445,9 +495,10 @@ def finish_rng_state():
     the code that asked for the deferral before it returns to the caller, so user code always sees the advanced state."""
     import numpy as np
     while _pending_state:
-        name, has_gauss, cached, host_state, host_pos, ev = _pending_state.pop()
+        name, has_gauss, cached, host, ev = _pending_state.pop()
         ev.synchronize()
-        np.random.set_state((name, host_state.numpy().view(np.uint32).copy(), int(host_pos.item()), has_gauss, cached))
+        words = host.numpy().view(np.uint32).copy()              # the pinned buffer is reused by the next hand-back
+        np.random.set_state((name, words[:624], int(words[624]), has_gauss, cached))
 
 
 def mt19937_random_sample(n, device, skip=0, advance=True, parallel=True, radix=True, raw=False, one_round=True, ranges=None):
@@ -471,8 +522,8 @@ def mt19937_random_sample(n, device, skip=0, advance=True, parallel=True, radix=
         st_in = torch.from_numpy(key.astype(np.uint32).view(np.int32)).to(dev)
     else:
         st_in = torch.from_numpy(key.astype(np.uint32).view(np.int32)).pin_memory().to(dev, non_blocking=True)
-    st_out = torch.empty(624, dtype=torch.int32, device=dev)
-    pos_out = torch.empty(1, dtype=torch.int32, device=dev)
+    st_out = torch.empty(625, dtype=torch.int32, device=dev)          # 624 state words, then pos: one buffer, one copy back
+    pos_out = st_out[624:]
     if raw and (skip != 0 or not parallel or n < (1 << 17)):
         raise ValueError("raw stream: skip = 0, the parallel generator and n >= 2^17 are required")
     n, skip, pos = int(n), int(skip), int(pos)
@@ -502,15 +553,13 @@ def mt19937_random_sample(n, device, skip=0, advance=True, parallel=True, radix=
                     nv.ptr(polys), levels, nv.ptr(rpolys), rlevels, nv.ptr(wpolys), nwin, nv.ptr(ws), wsb, nv.stream())
     if advance == "defer":
         finish_rng_state()                                           # at most one hand-back in flight
-        host_state = torch.empty(624, dtype=torch.int32).pin_memory()
-        host_pos = torch.empty(1, dtype=torch.int32).pin_memory()
+        host = _handback_buffer(dev)
         with torch.cuda.device(dev):
-            host_state.copy_(st_out, non_blocking=True)
-            host_pos.copy_(pos_out, non_blocking=True)
+            host.copy_(st_out, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
-        _pending_state.append((name, has_gauss, cached, host_state, host_pos, ev))
+        _pending_state.append((name, has_gauss, cached, host, ev))
     elif advance:
-        new_key = st_out.cpu().numpy().view(np.uint32)
-        np.random.set_state((name, new_key, int(pos_out.item()), has_gauss, cached))
+        words = st_out.cpu().numpy().view(np.uint32)
+        np.random.set_state((name, words[:624], int(words[624]), has_gauss, cached))
     return out

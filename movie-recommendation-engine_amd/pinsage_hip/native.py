@@ -65,6 +65,8 @@ PROTOTYPES = {
     "ps_linear": "i pqipipipipiipp",
     "ps_gcn_layer_workspace_bytes": "z qi",
     "ps_gcn_layer": "i pqipipipqippppiqipiippzp",
+    "ps_gcn_order": "i ppiqiqppp",
+    "ps_gcn_layer_ordered": "i pqipipipqippppiqipiippzppp",
     "ps_lsh_encode": "i pqipipip",
     "ps_hamming_topk_workspace_bytes": "z qqii",
     "ps_hamming_topk": "i pqpqiiqpppzp",

@@ -245,6 +245,21 @@ def walk_sample(graph, nodes, T, W=100, L=2, rng="numpy", seed=0, call=0, unifor
     return NeighborBatch(ids, counts, nvalid)
 
 
+_range_nodes_dev = {}
+
+
+def _range_nodes(start, stop, dev):
+    """arange(start, stop) as int64 on `dev`, made once per (device, start, stop): the item range a model samples is the same on
+    every step, and the arange kernel was a launch of its own in each.  Read-only: the kernels take it as const."""
+    key = (str(dev), int(start), int(stop))
+    t = _range_nodes_dev.get(key)
+    if t is None:
+        if len(_range_nodes_dev) >= 64:                  # callers that sweep many ranges: do not hold them all
+            _range_nodes_dev.clear()
+        t = _range_nodes_dev[key] = torch.arange(start, stop, dtype=torch.int64, device=dev)
+    return t
+
+
 def walk_sample_layers(graph, nodes, T, layers, W=100, L=2, rng="numpy", seed=0, call=0, uniforms=None,
                        stream_nodes=None, defer_state=False):
     """`layers` consecutive batch_sample_neighbors calls over the same start nodes (PinSage.get_embeddings,
@@ -268,7 +283,7 @@ def walk_sample_layers(graph, nodes, T, layers, W=100, L=2, rng="numpy", seed=0,
     if as_range is not None:
         if as_range.step != 1 or as_range.start < 0 or as_range.stop > graph.V:
             raise IndexError("list index out of range")
-        starts = torch.arange(as_range.start, as_range.stop, dtype=torch.int64, device=dev)
+        starts = _range_nodes(as_range.start, as_range.stop, dev)
     else:
         starts = _nodes_tensor(nodes, dev, graph.V)
     B = int(starts.numel())

@@ -162,9 +162,14 @@ class HipOps:
     def linear(self, x, W, b, x2=None, W2=None, relu=False, l2norm=False):
         return dense.linear(x, W, b, x2=x2, W2=W2, relu=relu, l2norm=l2norm)
 
-    def gcn_layer(self, x, W, b, h_full, batch, max_idx, W2):
-        """linear(x, W, b, x2=pool(h_full, batch, max_idx), W2=W2, relu=True, l2norm=True) in one launch (ps_gcn_layer)"""
-        return dense.gcn_layer(x, W, b, h_full, batch.ids, batch.counts, batch.nvalid, W2, max_idx=max_idx)
+    def gcn_layer(self, x, W, b, h_full, batch, max_idx, W2, order=None):
+        """linear(x, W, b, x2=pool(h_full, batch, max_idx), W2=W2, relu=True, l2norm=True) with the pooling inside the GEMM
+        (ps_gcn_layer); order: this layer's entry of gcn_orders"""
+        return dense.gcn_layer(x, W, b, h_full, batch.ids, batch.counts, batch.nvalid, W2, max_idx=max_idx, order=order)
+
+    def gcn_orders(self, batches, max_idx):
+        """the row orders of all layers' gcn_layer calls in one launch (ps_gcn_order), or None where gcn_layer makes its own"""
+        return dense.gcn_orders([b.ids for b in batches], [b.nvalid for b in batches], max_idx)
 
     def lsh_encode(self, x, A):
         return dense.lsh_encode(x, A)
@@ -300,6 +305,10 @@ class ShardedPinSage:
                     ready.append(side.record_event())
         else:
             batches.append(self._sample(nodes, T, shard))
+        # the layer GEMMs' row orders depend on the samples alone: all layers' in one launch, before the first GEMM
+        orders = None
+        if fused and self.fuse_self and hasattr(ops, "gcn_layer") and hasattr(ops, "gcn_orders"):
+            orders = ops.gcn_orders(batches, self.M - 1)
         if early_h is not None:
             torch.cuda.current_stream(dev).wait_event(early_ready)             # behind the sampling kernels enqueued above
         if x_full is not None and self.world > 1:
@@ -324,7 +333,8 @@ class ShardedPinSage:
             if side is not None:
                 torch.cuda.current_stream(dev).wait_event(ready[i])
             if self.fuse_self and hasattr(ops, "gcn_layer"):                  # pooling inside the layer GEMM
-                h = ops.gcn_layer(a_in, self._w(("l1", i), W1), b1, h_full, batches[i], self.M - 1, self._w(("l2", i), Wu[:, H:]))
+                kw = {} if orders is None else {"order": orders[i]}
+                h = ops.gcn_layer(a_in, self._w(("l1", i), W1), b1, h_full, batches[i], self.M - 1, self._w(("l2", i), Wu[:, H:]), **kw)
             else:
                 h_neigh = ops.pool(h_full, batches[i], self.M - 1)
                 h = ops.linear(a_in, self._w(("l1", i), W1), b1, x2=h_neigh, W2=self._w(("l2", i), Wu[:, H:]), relu=True, l2norm=True)
