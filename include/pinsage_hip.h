@@ -261,7 +261,23 @@ int ps_gcn_layer_ordered(const float *x, int64_t M, int K, const float *W, int l
 
 /* ---- a10: LSHIndex.build/search (utils/nearest_neighbors.py:28-68 -> faiss.IndexLSH) ---------
  * codes[n, nbits/8] : bit j = ( x . A[j,:] >= 0 ), LSB-first (faiss fvec2bitvec); A float[nbits,D].
- * flags: 0 or PS_WPERM (A stored by ps_permute_k). */
+ * flags: 0, PS_WPERM (A stored by ps_permute_k) or PS_LSH_STAGED (A points to an image of ps_lsh_stage; not with PS_WPERM:
+ * PS_EINVAL).  The same codes, bit for bit, from all three.
+ *
+ * ps_lsh_stage builds, once per matrix, what the staged path reads: A itself, A split into bf16 hi + lo in the order of the
+ * v_mfma_f32_32x32x16_bf16 operand, and an upper bound of every row norm.  ps_lsh_encode then decides x . A[j] >= 0 from a
+ * split-bf16 estimate wherever |estimate| > 2^-12 max(1, D / 256) (bound of |x|) (bound of |A[j]|), and from the exact fp32
+ * fmaf chain everywhere else (zero, non-finite and out-of-range rows always) -- csrc/lsh_filter.hip.
+ *   ps_lsh_stage_bytes(nbits, D) : size of the image; 0 where the staged path does not serve the shape (served: D in
+ *                                  {32, 64, 128, 256} -- a wave keeps its rows' operand fragments for the whole of D in
+ *                                  registers --, nbits % 32 == 0, nbits <= 1024); ps_lsh_stage / ps_lsh_encode return
+ *                                  PS_EUNSUPPORTED for such shapes and for A, staged or x not 16-byte aligned.
+ *   ps_lsh_stage                 : A float[nbits, D] row-major; staged_bytes below the size: PS_EINVAL.
+ * Under the environment switch PS_LSH_STATS=1 a staged ps_lsh_encode adds (dots decided, dots that took the exact chain) to
+ * the two uint64 counters at byte 16 of the image -- the one case in which an input is written; off by default. */
+#define PS_LSH_STAGED 8
+size_t ps_lsh_stage_bytes(int nbits, int D);
+int ps_lsh_stage(const float *A, int nbits, int D, void *staged, size_t staged_bytes, ps_stream_t stream);
 int ps_lsh_encode(const float *x, int64_t N, int D, const float *A, int nbits, uint8_t *codes, int flags, ps_stream_t stream);
 
 /* Hamming k-NN over all codes: k smallest by (distance, id), ascending; id = row + id_offset.

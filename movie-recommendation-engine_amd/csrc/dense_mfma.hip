@@ -1598,10 +1598,12 @@ extern "C" int ps_permute_k(const float *W, int64_t rows, int K, int ld, float *
 
 extern "C" int ps_lsh_encode(const float *x, int64_t N, int D, const float *A, int nbits, uint8_t *codes, int flags,
                              ps_stream_t stream) {
-    if (N < 0 || D <= 0 || nbits <= 0 || (flags & ~PS_WPERM)) return PS_EINVAL;
+    if (N < 0 || D <= 0 || nbits <= 0 || (flags & ~(PS_WPERM | PS_LSH_STAGED))) return PS_EINVAL;
+    if ((flags & PS_LSH_STAGED) && (flags & PS_WPERM)) return PS_EINVAL;      // a staged image has its own order
     if (nbits % 32 != 0) return PS_EUNSUPPORTED;      // codes are written as whole 32-bit ballot words
     if (N == 0) return PS_OK;
     if (!x || !A || !codes || reinterpret_cast<size_t>(codes) % 4 != 0) return PS_EINVAL;
+    if (flags & PS_LSH_STAGED) return psi_lsh_encode_staged(x, N, D, A, nbits, codes, stream);     // csrc/lsh_filter.hip
     GemmArgs g{x, N, D, A, D, nullptr, 0, nullptr, 0, nullptr, nbits, flags, nullptr, codes, nbits / 8};
     return launch_gemm<1>(g, ps_stream(stream));
 }

@@ -36,6 +36,9 @@ int psi_linear_grouped(const float *x, int64_t M, int K, const float *W, int ldw
 int psi_hardest_shared(const float *Q, int64_t B, int D, const float *X, int64_t N, int exclude_diag, unsigned long long *best,
                        ps_stream_t stream);
 
+// internal: ps_lsh_encode over an image of ps_lsh_stage (csrc/lsh_filter.hip: bf16 MFMA sign filter + exact fmaf recheck)
+int psi_lsh_encode_staged(const float *x, int64_t N, int D, const void *staged, int nbits, uint8_t *codes, ps_stream_t stream);
+
 __device__ __forceinline__ int ps_lane() { return threadIdx.x & 63; }
 
 // (similarity, candidate index) as ONE unsigned word whose integer order is "larger similarity first, then smaller index":

@@ -55,6 +55,45 @@ def stage_weight(W):
     return StagedWeight(out)
 
 
+class StagedLsh:
+    """An LSH rotation as ps_lsh_stage stores it (the fp32 matrix, its bf16 hi + lo split in MFMA operand order, a bound of
+    every row norm).  lsh_encode() takes it in place of the matrix (PS_LSH_STAGED): the same codes bit for bit, the signs
+    decided on the bf16 matrix pipe wherever that is beyond doubt and by the exact fmaf chain elsewhere (csrc/lsh_filter.hip).
+    `image` is the uint8 device buffer; stats() reads its two counters (they move under PS_LSH_STATS=1 only)."""
+    __slots__ = ("image", "shape")
+
+    def __init__(self, image, nbits, d):
+        self.image = image
+        self.shape = (nbits, d)
+
+    def size(self, i):
+        return self.shape[i]
+
+    def stats(self):
+        """(dots decided, dots that took the exact chain) since the image was staged"""
+        seen, flagged = self.image[16:32].view(torch.int64).tolist()
+        return seen, flagged
+
+
+def stage_lsh(A):
+    """StagedLsh of a [nbits, d] device rotation; where ps_lsh_stage does not serve the shape, and under PS_LSH_FILTER=0,
+    stage_weight(A) (the fp32 kernels)."""
+    if isinstance(A, (StagedLsh, StagedWeight)) or A is None:
+        return A
+    _require_cuda(A)
+    if os.environ.get("PS_LSH_FILTER", "1") == "0" or A.dim() != 2 or A.dtype != torch.float32:
+        return stage_weight(A)
+    nbits, d = A.size(0), A.size(1)
+    nbytes = nv.lib().ps_lsh_stage_bytes(nbits, d)
+    if nbytes == 0:
+        return stage_weight(A)
+    Ak = A.contiguous()
+    image = torch.empty(nbytes, dtype=torch.uint8, device=A.device)
+    with torch.cuda.device(A.device):
+        nv.call("ps_lsh_stage", nv.ptr(Ak), nbits, d, nv.ptr(image), nbytes, nv.stream())
+    return StagedLsh(image, nbits, d)
+
+
 def linear(x, W, b=None, x2=None, W2=None, relu=False, l2norm=False):
     """y = epi(x @ W.T (+ x2 @ W2.T) + b): nn.Linear / F.relu / torch.cat / F.normalize of
     PinSage.forward (reference model/pinsage.py:202,235-240,248-249) in one kernel.  W / W2: matrices or StagedWeights (both
@@ -176,20 +215,24 @@ def gcn_layer(x, W, b, h_full, ids, counts, nvalid, W2, wts=None, max_idx=None, 
 
 
 def lsh_encode(x, A):
-    """codes uint8[n, nbits/8]: bit j = (x . A[j] >= 0), LSB first (faiss IndexLSH.sa_encode).  A: matrix or StagedWeight."""
-    staged = isinstance(A, StagedWeight)
-    if staged:
+    """codes uint8[n, nbits/8]: bit j = (x . A[j] >= 0), LSB first (faiss IndexLSH.sa_encode).  A: matrix, StagedWeight or
+    StagedLsh."""
+    flags = nv.PS_LSH_STAGED if isinstance(A, StagedLsh) else nv.PS_WPERM if isinstance(A, StagedWeight) else 0
+    if flags == nv.PS_LSH_STAGED:
+        nbits, da, A = A.shape[0], A.shape[1], A.image
+    elif flags:
         A = A.t
     _require_cuda(x, A)
     x = x.contiguous()
     A = A.contiguous()
     n, d = x.size(0), x.size(1)
-    nbits = A.size(0)
-    if A.size(1) != d:
+    if flags != nv.PS_LSH_STAGED:
+        nbits, da = A.size(0), A.size(1)
+    if da != d:
         raise ValueError("projection matrix must be [nbits, dim]")
     codes = torch.empty((n, nbits // 8), dtype=torch.uint8, device=x.device)
     with torch.cuda.device(x.device):
-        nv.call("ps_lsh_encode", nv.ptr(x), n, d, nv.ptr(A), nbits, nv.ptr(codes), nv.PS_WPERM if staged else 0, nv.stream())
+        nv.call("ps_lsh_encode", nv.ptr(x), n, d, nv.ptr(A), nbits, nv.ptr(codes), flags, nv.stream())
     return codes
 
 

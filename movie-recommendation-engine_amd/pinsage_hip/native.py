@@ -20,6 +20,7 @@ PS_WALK_HALF_BUCKETS = 0x100
 PS_RELU = 1
 PS_L2NORM = 2
 PS_WPERM = 4
+PS_LSH_STAGED = 8
 PS_HN_PER_QUERY, PS_HN_EXCLUDE_DIAG = 1, 2
 PS_LOSS_SHARED, PS_LOSS_PER_QUERY, PS_LOSS_BATCH_HARD = 0, 1, 2
 PS_OK, PS_EINVAL, PS_ELAUNCH, PS_EWORKSPACE, PS_EUNSUPPORTED = 0, -1, -2, -3, -4      # status codes (include/pinsage_hip.h)
@@ -67,6 +68,8 @@ PROTOTYPES = {
     "ps_gcn_layer": "i pqipipipqippppiqipiippzp",
     "ps_gcn_order": "i ppiqiqppp",
     "ps_gcn_layer_ordered": "i pqipipipqippppiqipiippzppp",
+    "ps_lsh_stage_bytes": "z ii",
+    "ps_lsh_stage": "i piipzp",
     "ps_lsh_encode": "i pqipipip",
     "ps_hamming_topk_workspace_bytes": "z qqii",
     "ps_hamming_topk": "i pqpqiiqpppzp",

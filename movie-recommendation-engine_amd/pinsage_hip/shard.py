@@ -177,6 +177,9 @@ class HipOps:
     def stage_weight(self, W):
         return dense.stage_weight(W)
 
+    def stage_lsh(self, A):
+        return dense.stage_lsh(A)
+
     def lsh_planes(self, codes):
         return dense.lsh_expand(codes)
 
@@ -345,11 +348,12 @@ class ShardedPinSage:
     # -- LSH: LSHIndex.build / .search (utils/nearest_neighbors.py:28-68) over code shards -------------
     def _staged_A(self, A):
         """the LSH rotation in kernel staging order, remade when another matrix (or a modified one) is passed"""
-        if not hasattr(self.ops, "stage_weight") or not isinstance(A, torch.Tensor):
+        stage = getattr(self.ops, "stage_lsh", None) or getattr(self.ops, "stage_weight", None)
+        if stage is None or not isinstance(A, torch.Tensor):
             return A
         ent = self._staged.get("A")
         if ent is None or ent[0] is not A or ent[1] != A._version:
-            ent = self._staged["A"] = (A, A._version, self.ops.stage_weight(A))
+            ent = self._staged["A"] = (A, A._version, stage(A))
         return ent[2]
 
     # Catalogues whose whole code table is at most this many bytes are searched QUERY-sharded: the table is all-gathered once

@@ -25,7 +25,7 @@ names = sorted(set(F) | set(Wr), key=lambda k: -(F[k][0] + Wr[k][0]))
 lines = ["rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only) over `bench.py --full --steps %d --warmup 1 --no-cpu-baseline`" % steps,
          "values: KB per launch (mean over launches), as reported (FETCH_SIZE = TCC_EA0_RDREQ x 64 B; no wide-stream correction applied)", ""]
 for k in names:
-    own = any(t in k for t in ("walk_", "gemm_f32", "hamming", "importance_pool", "topk_merge", "slice_merge", "bound_select", "lsh_expand", "cdf_", "guide_", "pack_", "bucket_", "gather_kernel", "mt_", "spmm"))
+    own = any(t in k for t in ("walk_", "gemm_f32", "hamming", "importance_pool", "topk_merge", "slice_merge", "bound_select", "lsh_expand", "lsh_filter", "cdf_", "guide_", "pack_", "bucket_", "gather_kernel", "mt_", "spmm"))
     if not own:
         continue
     nf, nw = F[k][1] or 1, Wr[k][1] or 1
@@ -77,7 +77,8 @@ out = {"source": f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, ben
        "ps_importance_pool": per_launch(lambda k: k.startswith("importance_pool_kernel") or k.startswith("importance_pool4_kernel")),
        # template arguments <WM, WN, TM, TN, BK, EPI[, FAST]>: EPI 0 = ps_linear, 1 = ps_lsh_encode (one-tile and persistent kernels)
        "ps_linear": per_call(lambda k: _gemm_epi(k) == 0),
-       "ps_lsh_encode": per_call(lambda k: _gemm_epi(k) == 1),
+       # ... or, over a staged rotation (dense.stage_lsh, the step's default), lsh_filter_kernel<KS, JS> of csrc/lsh_filter.hip
+       "ps_lsh_encode": per_call(lambda k: _gemm_epi(k) == 1 or k.startswith("lsh_filter_kernel")),
        "ps_hamming_topk": per_launch(lambda k: k.startswith("hamming_scan_kernel") or k.startswith("topk_merge_kernel"))}
 json.dump(out, open(out_json, "w"), indent=1)
 print(open(out_txt).read())
