@@ -1,30 +1,18 @@
 """The MT19937 generator's hand-back: raw word 0 (stored by the chunk kernel itself), the first uniform, and the 625-word buffer
 -- 624 state words, then pos -- that comes back in one copy, against np.random.RandomState."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from mt_cases import state_at as _state_at, temper as _temper  # noqa: E402  (shared with tests/test_hip_mt_stream.py)
+
 pytestmark = pytest.mark.gpu
 
 N = 1 << 17                               # the smallest request that takes the parallel generator
-
-
-def _temper(y):
-    y = np.uint32(y)
-    y ^= y >> np.uint32(11)
-    y ^= (y << np.uint32(7)) & np.uint32(0x9d2c5680)
-    y ^= (y << np.uint32(15)) & np.uint32(0xefc60000)
-    y ^= y >> np.uint32(18)
-    return y
-
-
-def _state_at(pos_in, seed=1234):
-    """a RandomState whose position inside its 624-word block is pos_in"""
-    rs = np.random.RandomState(seed)
-    rs.random_sample(400)                                  # past the seeding block: pos = 800 - 624 = 176 into a generated block
-    key = rs.get_state()[1].copy()
-    rs.set_state(("MT19937", key, pos_in, 0, 0.0))
-    return rs
 
 
 def _raw_call(rs, n, ranges=None):
