@@ -215,6 +215,28 @@ int ps_importance_pool(const float *x, int64_t N, int H, const int32_t *ids, con
                        const float *wts, const int32_t *nvalid, int64_t B, int T, int64_t max_idx,
                        int renorm, float *out, ps_stream_t stream);
 
+/* ---- a9: AttentionAggregator's scores + softmax (model/aggregators.py:131-151) and MaxPoolingAggregator's maximum over the
+ * neighbours' transformed rows (:195-209), csrc/neigh_agg.hip.  Both keep slot j of row i iff j < min(nvalid[i], T) and
+ * 0 <= ids[i,j] < N (a negative nvalid[i] means 0); no other id is dereferenced.  Caller-allocated buffers, no allocation, no
+ * synchronisation; PS_EINVAL for a non-positive Hd / H / T or (B > 0) a null pointer; PS_OK for B == 0, whatever the
+ * pointers (the base of an empty buffer may be NULL).
+ *
+ * ps_attention_weights: u float[B,Hd], v float[N,Hd], w2 float[Hd], ids int32[B,T], nvalid int32[B], attn float[B,T].
+ * The attention MLP Linear(2C -> C), ReLU, Linear(C -> 1) over cat([self, neighbour]) (:147-150) with the first layer split by
+ * columns: u = self_features W1[:, :C]^T + b1 and v = features W1[:, C:]^T are two ps_linear calls, w2 the second layer's
+ * weight.  s_ij = sum_c w2[c] * max(u[i,c] + v[ids[i,j],c], 0) for a kept slot; attn[i,:] = softmax of the kept scores (row
+ * maximum subtracted, exponentials divided by their sum, :151); +0.0 in every slot that is not kept, all zeros for a row that keeps
+ * nothing (:132-135).  The second layer's bias shifts every score of a row alike and drops out of the softmax: it is not an
+ * argument.  The weighted sum of :154-157 is ps_importance_pool(x, ..., wts = attn, renorm = 0).
+ *
+ * ps_gather_max: x float[N,H], out float[B,H].  out[i,c] = max over the kept slots of x[ids[i,j], c], from -inf (never from 0);
+ * a NaN among the gathered values gives NaN (torch.max, :208); +0.0 in every column of a row that keeps nothing (:196-199).
+ * x is the MLP's output over all rows (ps_linear with PS_RELU), computed once instead of once per neighbour list. */
+int ps_attention_weights(const float *u, const float *v, int64_t N, int Hd, const float *w2, const int32_t *ids,
+                         const int32_t *nvalid, int64_t B, int T, float *attn, ps_stream_t stream);
+int ps_gather_max(const float *x, int64_t N, int H, const int32_t *ids, const int32_t *nvalid, int64_t B, int T, float *out,
+                  ps_stream_t stream);
+
 /* ---- a6: the dense layers of PinSage.forward (model/pinsage.py:202,235-240,248-249) ---------
  * y[M,N] = epilogue( x[M,K] W[N,K]^T (+ x2[M,K2] W2[N,K2]^T) + b ), fp32 MFMA, k-ordered fma chain.
  * x2/W2 eliminate torch.cat([h_self, h_neigh]) (:238): W = lin_update.weight[:, :H], W2 = [:, H:]

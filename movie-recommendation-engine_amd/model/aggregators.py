@@ -3,8 +3,9 @@ model/aggregators.py).  Same five classes, constructor arguments, parameter name
 signatures.  The gather + weighted reduce of Mean / Weighted / Importance aggregators runs on
 ps_importance_pool (one kernel for the whole batch instead of a python loop per node);
 ImportanceAggregator's Linear runs once on the pooled rows (sum_i w_i (W x_i + b) = W sum_i w_i x_i + b
-because the weights sum to 1), on the fp32-MFMA kernel.  Attention / MaxPooling stay torch code
-(batched over a padded neighbour tensor); they are not on the north-star path.
+because the weights sum to 1), on the fp32-MFMA kernel.  AttentionAggregator and MaxPoolingAggregator run on
+ps_attention_weights + ps_importance_pool and ps_linear + ps_gather_max for CUDA fp32 inputs outside autograd (no
+[B, T, C] tensor is ever built); CPU tensors, other dtypes and training keep the batched torch code (`_forward_torch`).
 """
 from __future__ import annotations
 
@@ -85,20 +86,58 @@ class WeightedAggregator(nn.Module):
         return out if features.is_cuda else out.to(features.device)
 
 
+def _pad_dev(neighbors, features):
+    """_pad's ids / nvalid on the device of `features`"""
+    ids, _, nvalid = _pad(neighbors, int(features.size(0)), mode="mean")
+    return torch.from_numpy(ids).to(features.device), torch.from_numpy(nvalid).to(features.device)
+
+
+def _off_tape(module, *tensors):
+    """may the call bypass autograd?  (ImportanceAggregator.forward's test, extended to the feature tensors)"""
+    return not (torch.is_grad_enabled() and (any(t.requires_grad for t in tensors) or
+                                             any(p.requires_grad for p in module.parameters())))
+
+
+def _cuda_fp32(t):
+    return t.is_cuda and t.dtype == torch.float32
+
+
 class AttentionAggregator(nn.Module):
-    """reference model/aggregators.py:93-160 (torch; batched over a padded neighbour tensor)"""
+    """reference model/aggregators.py:93-160.  HIP path: the first attention layer split by columns -- u = self W1[:, :C]^T + b1
+    over the B target rows and v = features W1[:, C:]^T over all rows, two ps_linear calls -- then ps_attention_weights
+    (scores + softmax over a gather of T rows of v) and ps_importance_pool with those weights (a gather of T rows of features).
+    The second layer's bias shifts all scores of a row alike and drops out of the softmax."""
 
     def __init__(self, in_channels):
         super().__init__()
         self.attention = nn.Sequential(nn.Linear(in_channels * 2, in_channels), nn.ReLU(), nn.Linear(in_channels, 1))
 
     def forward(self, features, neighbors, self_features=None):
-        if self_features is None:
-            self_features = features
-        ids, _, nvalid = _pad(neighbors, int(features.size(0)), mode="mean")
+        sf = features if self_features is None else self_features
+        if not (_cuda_fp32(features) and _cuda_fp32(sf) and _off_tape(self, features, sf)) or features.dim() != 2 \
+                or sf.dim() != 2 or sf.size(0) < len(neighbors) or sf.size(1) != features.size(1) \
+                or self.attention[0].in_features != 2 * features.size(1):
+            return self._forward_torch(features, neighbors, self_features)       # malformed calls raise what they always raised
+        return self._hip_padded(features, *_pad_dev(neighbors, features), sf)
+
+    def _hip_padded(self, features, ids, nvalid, self_features):
+        """the HIP path over padded device tensors (ids int32 [B,T], nvalid int32 [B])"""
+        dev, C, B = features.device, int(features.size(1)), int(ids.size(0))
+        W1, b1 = self.attention[0].weight.detach().to(dev), self.attention[0].bias.detach().to(dev)
+        w2 = self.attention[2].weight.detach().to(dev).reshape(-1)
+        with torch.no_grad():
+            u = dense.linear(self_features[:B], W1[:, :C], b1)
+            v = dense.linear(features, W1[:, C:])
+            return sampling.attention_pool(features, u, v, w2, ids, nvalid)
+
+    def _forward_torch(self, features, neighbors, self_features=None):
+        """batched over a padded neighbour tensor (CPU tensors, other dtypes, training)"""
+        return self._torch_padded(features, *_pad_dev(neighbors, features), features if self_features is None else self_features)
+
+    def _torch_padded(self, features, ids, nvalid, self_features):
         dev = features.device
-        idt = torch.from_numpy(ids).to(dev).long().clamp(min=0)
-        mask = torch.arange(ids.shape[1], device=dev)[None, :] < torch.from_numpy(nvalid).to(dev)[:, None]
+        idt = ids.long().clamp(min=0)
+        mask = torch.arange(ids.shape[1], device=dev)[None, :] < nvalid[:, None]
         nbr = features[idt]                                               # [B,T,C]
         B = idt.size(0)
         selfe = self_features[:B].unsqueeze(1).expand(-1, idt.size(1), -1)
@@ -112,17 +151,34 @@ class AttentionAggregator(nn.Module):
 
 
 class MaxPoolingAggregator(nn.Module):
-    """reference model/aggregators.py:162-211 (torch; mlp applied once per node, masked max)"""
+    """reference model/aggregators.py:162-211.  HIP path: the MLP once over all rows (ps_linear with its ReLU epilogue), then
+    ps_gather_max over the neighbour lists."""
 
     def __init__(self, in_channels, out_channels):
         super().__init__()
         self.mlp = nn.Sequential(nn.Linear(in_channels, out_channels), nn.ReLU())
 
     def forward(self, features, neighbors):
-        ids, _, nvalid = _pad(neighbors, int(features.size(0)), mode="mean")
+        if not (_cuda_fp32(features) and _off_tape(self, features)) or features.dim() != 2 \
+                or features.size(1) != self.mlp[0].in_features:
+            return self._forward_torch(features, neighbors)
+        return self._hip_padded(features, *_pad_dev(neighbors, features))
+
+    def _hip_padded(self, features, ids, nvalid):
+        """the HIP path over padded device tensors (ids int32 [B,T], nvalid int32 [B])"""
         dev = features.device
-        idt = torch.from_numpy(ids).to(dev).long().clamp(min=0)
-        mask = torch.arange(ids.shape[1], device=dev)[None, :] < torch.from_numpy(nvalid).to(dev)[:, None]
+        with torch.no_grad():
+            t = dense.linear(features, self.mlp[0].weight.detach().to(dev), self.mlp[0].bias.detach().to(dev), relu=True)
+            return sampling.gather_max(t, ids, nvalid)
+
+    def _forward_torch(self, features, neighbors):
+        """mlp applied once per node, masked max (CPU tensors, other dtypes, training)"""
+        return self._torch_padded(features, *_pad_dev(neighbors, features))
+
+    def _torch_padded(self, features, ids, nvalid):
+        dev = features.device
+        idt = ids.long().clamp(min=0)
+        mask = torch.arange(ids.shape[1], device=dev)[None, :] < nvalid[:, None]
         t = self.mlp(features)[idt]
         t = t.masked_fill(~mask.unsqueeze(2), float("-inf"))
         out = t.max(dim=1).values

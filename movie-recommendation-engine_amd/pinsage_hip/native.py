@@ -62,6 +62,8 @@ PROTOTYPES = {
     "ps_mt19937_workspace_bytes": "z qq",
     "ps_mt19937_random_sample": "i piqqppppipipipzp",
     "ps_importance_pool": "i pqippppqiqipp",
+    "ps_attention_weights": "i ppqipppqipp",
+    "ps_gather_max": "i pqippqipp",
     "ps_permute_k": "i pqiipp",
     "ps_linear": "i pqipipipipiipp",
     "ps_gcn_layer_workspace_bytes": "z qi",

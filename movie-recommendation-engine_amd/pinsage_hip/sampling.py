@@ -393,6 +393,56 @@ def importance_pool(x, batch: NeighborBatch = None, ids=None, counts=None, wts=N
     return out
 
 
+def _rows_fp32(name, *tensors):
+    out = []
+    for t in tensors:
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} expects fp32 features")
+        out.append(t.contiguous())
+    return out
+
+
+def attention_weights(u, v, w2, ids, nvalid):
+    """attn[B,T] = softmax over the kept slots j of sum_c w2[c] * relu(u[i,c] + v[ids[i,j],c]), +0.0 elsewhere
+    (AttentionAggregator's scores, reference model/aggregators.py:131-151; u / v: the first attention layer split by columns,
+    include/pinsage_hip.h)."""
+    u, v, w2 = _rows_fp32("attention_weights", u, v, w2.reshape(-1))
+    if ids.dtype != torch.int32 or nvalid.dtype != torch.int32:
+        raise TypeError("ids / nvalid must be int32")
+    B, T = ids.size(0), ids.size(1)
+    N, Hd = v.size(0), v.size(1)
+    if u.size(0) != B or u.size(1) != Hd or w2.numel() != Hd or nvalid.numel() != B:
+        raise ValueError(f"shape mismatch: u {tuple(u.shape)}, v {tuple(v.shape)}, w2 {tuple(w2.shape)}, ids {tuple(ids.shape)}")
+    attn = torch.empty((B, T), dtype=torch.float32, device=v.device)
+    with torch.cuda.device(v.device):
+        nv.call("ps_attention_weights", nv.ptr(u), nv.ptr(v), N, Hd, nv.ptr(w2), nv.ptr(ids), nv.ptr(nvalid), B, T, nv.ptr(attn),
+                nv.stream())
+    return attn
+
+
+def gather_max(x, ids, nvalid):
+    """out[B,H] = max over the kept slots j of x[ids[i,j]]; zeros for a row that keeps nothing (MaxPoolingAggregator's
+    torch.max over the neighbours, reference model/aggregators.py:195-209)."""
+    x, = _rows_fp32("gather_max", x)
+    if ids.dtype != torch.int32 or nvalid.dtype != torch.int32:
+        raise TypeError("ids / nvalid must be int32")
+    B, T = ids.size(0), ids.size(1)
+    N, H = x.size(0), x.size(1)
+    if nvalid.numel() != B:
+        raise ValueError(f"shape mismatch: ids {tuple(ids.shape)}, nvalid {tuple(nvalid.shape)}")
+    out = torch.empty((B, H), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        nv.call("ps_gather_max", nv.ptr(x), N, H, nv.ptr(ids), nv.ptr(nvalid), B, T, nv.ptr(out), nv.stream())
+    return out
+
+
+def attention_pool(x, u, v, w2, ids, nvalid):
+    """out[B,C] = sum_j attn[i,j] * x[ids[i,j]] with attn = attention_weights(u, v, w2, ids, nvalid): AttentionAggregator.forward
+    (reference model/aggregators.py:131-158) as two gathers -- T rows of v, then T rows of x, per output row."""
+    attn = attention_weights(u, v, w2, ids, nvalid)
+    return importance_pool(x, ids=ids, wts=attn, nvalid=nvalid, renorm=False)
+
+
 class PoolFn(torch.autograd.Function):
     """Differentiable ps_importance_pool: the forward is the kernel, the backward scatter-adds w_ij * grad_out_i
     into the feature rows (d out_i / d x_r = sum over the slots j of row i with ids_ij == r of w_ij).  The weights
