@@ -237,6 +237,35 @@ int ps_attention_weights(const float *u, const float *v, int64_t N, int Hd, cons
 int ps_gather_max(const float *x, int64_t N, int H, const int32_t *ids, const int32_t *nvalid, int64_t B, int T, float *out,
                   ps_stream_t stream);
 
+/* ---- a9 (model/layers.py): nn.BatchNorm1d of GraphConvLayer.forward with the ReLU and F.normalize behind it (model/layers.py:68-75),
+ * csrc/batch_norm.hip.  Caller-allocated buffers, no allocation, no synchronisation, no atomics.
+ *
+ * ps_bn_batch_stats: z float[M,N] (dense rows), gamma float[N] -> mean, var, scale float[N], always written:
+ *   S = sum_r z[r,c], Q = sum_r z[r,c]^2, both accumulated in fp64 (the square of an fp32 value is exact there) in ONE pass over z;
+ *   mean = fp32(S / M); var64 = max(Q / M - (S / M)^2, 0), the biased batch variance, var = fp32(var64);
+ *   scale = fp32(gamma / sqrt(var64 + eps)), in fp64.
+ * running_mean / running_var float[N], both or neither (one alone: PS_EINVAL), are updated in place, in fp64 with one rounding:
+ *   running_mean = (1 - momentum) running_mean + momentum S / M,
+ *   running_var  = (1 - momentum) running_var  + momentum var64 M / (M - 1)     (the unbiased variance, as torch tracks it).
+ * eps and momentum arrive as fp32 -- the precision torch's own fp32 kernels use them at -- and are widened to fp64.
+ * Summation order: the rows are cut into ceil(M / 128) partitions of 128 consecutive rows (a function of M only); within a
+ * partition four strided row subsets are summed sequentially and added in subset order; the partitions are added in ascending
+ * order.  Equal inputs give equal bits, whatever the workspace held before the call.
+ * workspace: ps_bn_stats_workspace_bytes(M, N) bytes (16 N bytes per partition), 8-byte aligned, not preserved between calls.
+ * PS_EINVAL for M < 2 (the unbiased variance does not exist), N < 1, a null pointer or a short workspace.
+ *
+ * ps_bn_apply: y[r,c] = epilogue(fmaf(z[r,c] - mean[c], scale[c], beta[c])), one wave per row.  flags: PS_RELU (t < 0 ? +0 : t),
+ * PS_L2NORM (the row divided by fmaxf(sqrtf(sum_c t^2), 1e-12f); the sum is a per-lane fmaf chain over the lane's columns in
+ * ascending order, then the wave sum of the other row kernels); any other bit: PS_EINVAL.  y may be z: in place gives the bits of
+ * out of place.  PS_OK for M == 0, whatever the pointers; PS_EINVAL for N < 1 or (M > 0) a null pointer.
+ * With mean = running_mean and scale = gamma / sqrt(running_var + eps) this is eval-mode batch norm. */
+size_t ps_bn_stats_workspace_bytes(int64_t M, int N);
+int ps_bn_batch_stats(const float *z, int64_t M, int N, const float *gamma, float eps, float momentum, float *running_mean,
+                      float *running_var, float *mean, float *var, float *scale, void *workspace, size_t workspace_bytes,
+                      ps_stream_t stream);
+int ps_bn_apply(const float *z, int64_t M, int N, const float *mean, const float *scale, const float *beta, int flags, float *y,
+                ps_stream_t stream);
+
 /* ---- a6: the dense layers of PinSage.forward (model/pinsage.py:202,235-240,248-249) ---------
  * y[M,N] = epilogue( x[M,K] W[N,K]^T (+ x2[M,K2] W2[N,K2]^T) + b ), fp32 MFMA, k-ordered fma chain.
  * x2/W2 eliminate torch.cat([h_self, h_neigh]) (:238): W = lin_update.weight[:, :H], W2 = [:, H:]

@@ -1,0 +1,263 @@
+// batch_norm.hip -- nn.BatchNorm1d of GraphConvLayer (reference model/layers.py:68-75) on gfx950: column statistics of z[M, N]
+// and the per-column affine map with the layer's ReLU and F.normalize behind it (two HBM-bound sweeps over z).
+//
+// ps_bn_batch_stats  one pass over z.  The rows are cut into partitions of BN_ROWS consecutive rows (a function of M only); a
+//                    workgroup takes one partition and 64 * VEC columns, its four waves take the partition's rows r0 + w,
+//                    r0 + w + 4, ... and every lane adds its columns' z and z * z in fp64 (the square of an fp32 value is exact
+//                    there).  The four waves' sums are added in wave order through LDS and written to the workspace; a second
+//                    kernel adds the partitions in ascending order, one lane per column, and makes mean / var / scale and the
+//                    running update.  No atomics, every workspace word that is read was written by this call: equal inputs give
+//                    equal bits.
+// ps_bn_apply        one wave per row, as importance_pool_kernel / gather_max_kernel: 16 B per lane when N % 4 == 0 and the
+//                    pointers allow it, a scalar sweep otherwise, grid-stride over the rows.  Rows of up to KEEP sweeps stay in
+//                    registers between the sum of squares and the division; longer rows are read a second time (by the lane
+//                    that writes the same addresses afterwards, so y may be z).
+#include "ps_common.h"
+
+namespace {
+
+constexpr int BN_ROWS = 128;       // rows per partition of the statistics pass
+constexpr int BN_UNROLL = 8;       // rows a wave has in flight
+constexpr int KEEP = 4;            // sweeps of a row that ps_bn_apply keeps in registers
+
+template <int VEC>
+__device__ __forceinline__ void load_vec(const float *__restrict__ p, bool ok, float (&r)[VEC]) {
+    if (VEC == 4) {
+        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ok) q = *reinterpret_cast<const float4 *>(p);
+        r[0] = q.x; r[1 % VEC] = q.y; r[2 % VEC] = q.z; r[3 % VEC] = q.w;
+    } else {
+        r[0] = ok ? p[0] : 0.f;
+    }
+}
+
+template <int VEC>
+__device__ __forceinline__ void store_vec(float *__restrict__ p, const float (&r)[VEC]) {
+    if (VEC == 4) *reinterpret_cast<float4 *>(p) = make_float4(r[0], r[1 % VEC], r[2 % VEC], r[3 % VEC]);
+    else p[0] = r[0];
+}
+
+// part[p, 0, c] = sum of z[r, c], part[p, 1, c] = sum of z[r, c]^2 over the rows r of partition p (double[P, 2, N])
+template <int VEC>
+__global__ __launch_bounds__(256) void bn_partial_kernel(const float *__restrict__ z, int64_t M, int N, int64_t P,
+                                                         double *__restrict__ part) {
+    __shared__ double sh[3][2][64 * VEC];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int col = (int)blockIdx.y * 64 * VEC + lane * VEC;
+    const bool cact = col < N;
+    for (int64_t p = blockIdx.x; p < P; p += gridDim.x) {
+        const int64_t r0 = p * BN_ROWS;
+        const int64_t r1 = (r0 + BN_ROWS < M) ? r0 + BN_ROWS : M;
+        double s[VEC], q[VEC];
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) { s[e] = 0.0; q[e] = 0.0; }
+        for (int64_t r = r0 + wave; r < r1; r += 4 * BN_UNROLL) {
+            float v[BN_UNROLL][VEC];
+#pragma unroll
+            for (int t = 0; t < BN_UNROLL; ++t) {
+                const int64_t rr = r + 4 * t;
+                load_vec<VEC>(z + rr * N + col, cact && rr < r1, v[t]);
+            }
+#pragma unroll
+            for (int t = 0; t < BN_UNROLL; ++t)                          // a row past the partition adds +0.0 twice: no change
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) {
+                    const double d = (double)v[t][e];
+                    s[e] += d;
+                    q[e] += d * d;
+                }
+        }
+        if (wave > 0) {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                sh[wave - 1][0][lane * VEC + e] = s[e];
+                sh[wave - 1][1][lane * VEC + e] = q[e];
+            }
+        }
+        __syncthreads();
+        if (wave == 0 && cact) {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                double ss = s[e], qq = q[e];
+#pragma unroll
+                for (int w = 0; w < 3; ++w) {
+                    ss += sh[w][0][lane * VEC + e];
+                    qq += sh[w][1][lane * VEC + e];
+                }
+                part[(p * 2 + 0) * N + col + e] = ss;
+                part[(p * 2 + 1) * N + col + e] = qq;
+            }
+        }
+        __syncthreads();                                                 // sh is reused by the next partition
+    }
+}
+
+__global__ __launch_bounds__(64) void bn_finish_kernel(const double *__restrict__ part, int64_t P, int64_t M, int N,
+                                                       const float *__restrict__ gamma, double eps, double momentum,
+                                                       float *__restrict__ running_mean, float *__restrict__ running_var,
+                                                       float *__restrict__ mean, float *__restrict__ var,
+                                                       float *__restrict__ scale) {
+    for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < N; c += gridDim.x * blockDim.x) {
+        double S = 0.0, Q = 0.0;
+#pragma unroll 32                                                        // the loads of 32 partitions in flight ahead of the two add chains
+        for (int64_t p = 0; p < P; ++p) {
+            S += part[(p * 2 + 0) * N + c];
+            Q += part[(p * 2 + 1) * N + c];
+        }
+        const double m = S / (double)M;
+        double v = Q / (double)M - m * m;
+        v = v > 0.0 ? v : 0.0;
+        mean[c] = (float)m;
+        var[c] = (float)v;
+        scale[c] = (float)((double)gamma[c] / sqrt(v + eps));
+        if (running_mean) {
+            const double unbiased = v * ((double)M / (double)(M - 1));
+            running_mean[c] = (float)((1.0 - momentum) * (double)running_mean[c] + momentum * m);
+            running_var[c] = (float)((1.0 - momentum) * (double)running_var[c] + momentum * unbiased);
+        }
+    }
+}
+
+// t = fmaf(z - mean, scale, beta), ReLU when RELU
+template <int VEC>
+__device__ __forceinline__ void bn_affine(const float (&zz)[VEC], const float (&mm)[VEC], const float (&sc)[VEC],
+                                          const float (&bb)[VEC], bool relu, float (&t)[VEC]) {
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+        const float a = fmaf(zz[e] - mm[e], sc[e], bb[e]);
+        t[e] = (relu && a < 0.f) ? 0.f : a;
+    }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void bn_apply_kernel(const float *z, int64_t M, int N, const float *__restrict__ mean,
+                                                       const float *__restrict__ scale, const float *__restrict__ beta,
+                                                       int flags, float *y) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const int nwaves = (int)((gridDim.x * blockDim.x) >> 6);
+    const int chunk = 64 * VEC;
+    const bool relu = (flags & PS_RELU) != 0, l2 = (flags & PS_L2NORM) != 0;
+    const bool fits = N <= KEEP * chunk;
+    // the first KEEP sweeps' share of the column vectors is the same for every row
+    float m0[KEEP][VEC], s0[KEEP][VEC], b0[KEEP][VEC];
+#pragma unroll
+    for (int k = 0; k < KEEP; ++k) {
+        const int col = k * chunk + lane * VEC;
+        load_vec<VEC>(mean + col, col < N, m0[k]);
+        load_vec<VEC>(scale + col, col < N, s0[k]);
+        load_vec<VEC>(beta + col, col < N, b0[k]);
+    }
+    for (int64_t i = wave; i < M; i += nwaves) {
+        const float *zr = z + i * N;
+        float *yr = y + i * N;
+        float t[KEEP][VEC];
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k < KEEP; ++k) {
+            const int col = k * chunk + lane * VEC;
+            float zz[VEC];
+            load_vec<VEC>(zr + col, col < N, zz);
+            bn_affine<VEC>(zz, m0[k], s0[k], b0[k], relu, t[k]);         // a column past N: fmaf(0 - 0, 0, 0) = +0.0
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc = fmaf(t[k][e], t[k][e], acc);
+        }
+        if (!fits && l2) {
+            for (int c0 = KEEP * chunk; c0 < N; c0 += chunk) {
+                const int col = c0 + lane * VEC;
+                const bool cact = col < N;
+                float zz[VEC], mm[VEC], sc[VEC], bb[VEC], tt[VEC];
+                load_vec<VEC>(zr + col, cact, zz);
+                load_vec<VEC>(mean + col, cact, mm);
+                load_vec<VEC>(scale + col, cact, sc);
+                load_vec<VEC>(beta + col, cact, bb);
+                bn_affine<VEC>(zz, mm, sc, bb, relu, tt);
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) acc = fmaf(tt[e], tt[e], acc);
+            }
+        }
+        float nrm = 1.f;
+        if (l2) nrm = fmaxf(sqrtf(ps_wave_sum_f32(acc)), 1e-12f);
+#pragma unroll
+        for (int k = 0; k < KEEP; ++k) {
+            const int col = k * chunk + lane * VEC;
+            if (col < N) {
+                float o[VEC];
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) o[e] = l2 ? t[k][e] / nrm : t[k][e];
+                store_vec<VEC>(yr + col, o);
+            }
+        }
+        if (!fits) {
+            // the rest of a long row: every lane reads again what it is about to overwrite (y may be z)
+            for (int c0 = KEEP * chunk; c0 < N; c0 += chunk) {
+                const int col = c0 + lane * VEC;
+                const bool cact = col < N;
+                float zz[VEC], mm[VEC], sc[VEC], bb[VEC], tt[VEC];
+                load_vec<VEC>(zr + col, cact, zz);
+                load_vec<VEC>(mean + col, cact, mm);
+                load_vec<VEC>(scale + col, cact, sc);
+                load_vec<VEC>(beta + col, cact, bb);
+                bn_affine<VEC>(zz, mm, sc, bb, relu, tt);
+                if (cact) {
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) tt[e] = l2 ? tt[e] / nrm : tt[e];
+                    store_vec<VEC>(yr + col, tt);
+                }
+            }
+        }
+    }
+}
+
+inline int64_t bn_partitions(int64_t M) { return ps_cdiv(M, BN_ROWS); }
+
+inline unsigned row_grid(int64_t B) {          // 4 waves (rows) per workgroup; beyond 16 384 waves the rows are strided over
+    int64_t grid = ps_cdiv(B, 4);
+    return (unsigned)(grid > 256 * 16 ? 256 * 16 : grid);
+}
+
+}  // namespace
+
+extern "C" size_t ps_bn_stats_workspace_bytes(int64_t M, int N) {
+    if (M < 2 || N < 1) return 0;
+    return (size_t)bn_partitions(M) * 2 * (size_t)N * sizeof(double);
+}
+
+extern "C" int ps_bn_batch_stats(const float *z, int64_t M, int N, const float *gamma, float eps, float momentum,
+                                 float *running_mean, float *running_var, float *mean, float *var, float *scale,
+                                 void *workspace, size_t workspace_bytes, ps_stream_t stream) {
+    if (M < 2 || N < 1 || !z || !gamma || !mean || !var || !scale || !workspace) return PS_EINVAL;
+    if ((running_mean == nullptr) != (running_var == nullptr)) return PS_EINVAL;
+    if (workspace_bytes < ps_bn_stats_workspace_bytes(M, N) || reinterpret_cast<size_t>(workspace) % 8 != 0) return PS_EINVAL;
+    hipStream_t st = ps_stream(stream);
+    const int64_t P = bn_partitions(M);
+    double *part = static_cast<double *>(workspace);
+    const unsigned gx = (unsigned)(P > 65535 ? 65535 : P);
+    const bool vec4 = (N % 4 == 0) && (reinterpret_cast<size_t>(z) % 16 == 0);
+    if (vec4)
+        hipLaunchKernelGGL(bn_partial_kernel<4>, dim3(gx, (unsigned)ps_cdiv(N, 256)), dim3(256), 0, st, z, M, N, P, part);
+    else
+        hipLaunchKernelGGL(bn_partial_kernel<1>, dim3(gx, (unsigned)ps_cdiv(N, 64)), dim3(256), 0, st, z, M, N, P, part);
+    PS_CHECK_LAUNCH();
+    hipLaunchKernelGGL(bn_finish_kernel, dim3((unsigned)ps_cdiv(N, 64)), dim3(64), 0, st, part, P, M, N, gamma, (double)eps,
+                       (double)momentum, running_mean, running_var, mean, var, scale);
+    PS_CHECK_LAUNCH();
+    return PS_OK;
+}
+
+extern "C" int ps_bn_apply(const float *z, int64_t M, int N, const float *mean, const float *scale, const float *beta, int flags,
+                           float *y, ps_stream_t stream) {
+    if (M < 0 || N < 1 || (flags & ~(PS_RELU | PS_L2NORM))) return PS_EINVAL;
+    if (M == 0) return PS_OK;                                 // before the pointers: an empty tensor's base is NULL
+    if (!z || !mean || !scale || !beta || !y) return PS_EINVAL;
+    hipStream_t st = ps_stream(stream);
+    const bool vec4 = (N % 4 == 0) && ((reinterpret_cast<size_t>(z) | reinterpret_cast<size_t>(y) | reinterpret_cast<size_t>(mean) |
+                                        reinterpret_cast<size_t>(scale) | reinterpret_cast<size_t>(beta)) % 16 == 0);
+    if (vec4)
+        hipLaunchKernelGGL(bn_apply_kernel<4>, dim3(row_grid(M)), dim3(256), 0, st, z, M, N, mean, scale, beta, flags, y);
+    else
+        hipLaunchKernelGGL(bn_apply_kernel<1>, dim3(row_grid(M)), dim3(256), 0, st, z, M, N, mean, scale, beta, flags, y);
+    PS_CHECK_LAUNCH();
+    return PS_OK;
+}

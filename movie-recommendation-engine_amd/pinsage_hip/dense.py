@@ -129,6 +129,68 @@ def linear(x, W, b=None, x2=None, W2=None, relu=False, l2norm=False):
     return y
 
 
+BN_STATS_ROWS = 128       # rows per partition of ps_bn_batch_stats' fixed summation order (csrc/batch_norm.hip)
+
+
+def _fp32_vec(name, t, n, device):
+    if t.dtype != torch.float32:
+        raise TypeError("fp32 expected")
+    if t.dim() != 1 or t.numel() != n or t.device != device:
+        raise ValueError(f"{name} must be a float32 [{n}] vector on the device of z")
+    return t.contiguous()
+
+
+def batch_norm_stats(z, gamma, eps, momentum, running_mean=None, running_var=None):
+    """(mean, var, scale) fp32 [N] of the columns of z [M, N], M >= 2 (ps_bn_batch_stats): the batch mean, the biased batch
+    variance and gamma / sqrt(var + eps), from fp64 sums made in one pass over z in a fixed order -- the statistics training-mode
+    nn.BatchNorm1d normalises with.  running_mean / running_var (both or neither) are updated IN PLACE as that module updates
+    them: (1 - momentum) old + momentum new, the variance entering with the unbiased factor M / (M - 1)."""
+    _require_cuda(z, gamma, running_mean, running_var)
+    if z.dtype != torch.float32:
+        raise TypeError("fp32 expected")
+    if z.dim() != 2:
+        raise ValueError("2-D matrix expected")
+    if (running_mean is None) != (running_var is None):
+        raise ValueError("running_mean and running_var: both or neither")
+    z = z.contiguous()
+    M, N = z.size(0), z.size(1)
+    gamma = _fp32_vec("gamma", gamma, N, z.device)
+    for name, t in (("running_mean", running_mean), ("running_var", running_var)):
+        if t is not None and (_fp32_vec(name, t, N, z.device) is not t or not t.is_contiguous()):
+            raise ValueError(f"{name} is updated in place: it must be contiguous")
+    mean, var, scale = (torch.empty(N, dtype=torch.float32, device=z.device) for _ in range(3))
+    ws, wsb = nv.workspace("ps_bn_stats_workspace_bytes", z.device, M, N)
+    with torch.cuda.device(z.device):
+        nv.call("ps_bn_batch_stats", nv.ptr(z), M, N, nv.ptr(gamma), float(eps), float(momentum), nv.ptr(running_mean),
+                nv.ptr(running_var), nv.ptr(mean), nv.ptr(var), nv.ptr(scale), nv.ptr(ws), wsb, nv.stream())
+    return mean, var, scale
+
+
+def batch_norm_apply(z, mean, scale, beta, relu, l2norm, out=None):
+    """y = epi((z - mean) * scale + beta) per column of z [M, N] (ps_bn_apply): the normalisation of nn.BatchNorm1d with the
+    F.relu / F.normalize of GraphConvLayer.forward behind it, one wave per row.  out: a contiguous fp32 [M, N] device tensor to
+    write into; out=z works in place and gives the bits of a new tensor."""
+    _require_cuda(z, mean, scale, beta, out)
+    if z.dtype != torch.float32:
+        raise TypeError("fp32 expected")
+    if z.dim() != 2:
+        raise ValueError("2-D matrix expected")
+    if out is None or out is not z:
+        z = z.contiguous()
+    elif not z.is_contiguous():
+        raise ValueError("in place: z must be contiguous")
+    M, N = z.size(0), z.size(1)
+    mean, scale, beta = (_fp32_vec(n, t, N, z.device) for n, t in (("mean", mean), ("scale", scale), ("beta", beta)))
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=z.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (M, N) or not out.is_contiguous() or out.device != z.device:
+        raise ValueError("out must be a contiguous fp32 [M, N] tensor on the device of z")
+    flags = (nv.PS_RELU if relu else 0) | (nv.PS_L2NORM if l2norm else 0)
+    with torch.cuda.device(z.device):
+        nv.call("ps_bn_apply", nv.ptr(z), M, N, nv.ptr(mean), nv.ptr(scale), nv.ptr(beta), flags, nv.ptr(out), nv.stream())
+    return out
+
+
 GCN_MIN_ROWS, GCN_MAX_T = 64 * 384, 16      # the M / T gates of ps_gcn_layer: gcn_orders makes no order the layer call would refuse
 
 

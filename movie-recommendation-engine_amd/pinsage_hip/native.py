@@ -64,6 +64,9 @@ PROTOTYPES = {
     "ps_importance_pool": "i pqippppqiqipp",
     "ps_attention_weights": "i ppqipppqipp",
     "ps_gather_max": "i pqippqipp",
+    "ps_bn_stats_workspace_bytes": "z qi",
+    "ps_bn_batch_stats": "i pqipffppppppzp",
+    "ps_bn_apply": "i pqipppipp",
     "ps_permute_k": "i pqiipp",
     "ps_linear": "i pqipipipipiipp",
     "ps_gcn_layer_workspace_bytes": "z qi",
