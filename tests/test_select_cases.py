@@ -1,0 +1,187 @@
+"""The planted cases of the walk sampler's count and select phases (tests/helpers/select_cases.py) prove their own coverage
+here, without a GPU: every case reaches the situation it is named for (by the restated table arithmetic), the reference's
+three lines (Counter over walk[1:], sorted by count, [:T]) equal the C oracle on every case at every T, ten deliberate slips of
+the selection each change what a named case expects, and the constants restated in the helper still stand in
+csrc/walk_sample.hip.  tests/test_hip_select_matrix.py then runs the kernels on the same cases."""
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.join(HERE, "helpers"))
+import select_cases as sc  # noqa: E402
+import walk_cases as wc  # noqa: E402
+
+LISTED_P = {1, 51, 64, 65, 102, 128, 204, 256, 257, 409, 512, 819, 1024, 1025, 1638, 2048, 3276, 4096}
+
+
+def test_the_graph_is_what_the_cases_assume():
+    for sinks in (False, True):
+        cg = sc.case_graph(sinks)[0]
+        deg = np.diff(cg.rowptr)
+        ordinary = sc.is_ordinary(np.arange(sc.V))
+        sink = sc.is_sink(np.arange(sc.V)) if sinks else np.zeros(sc.V, dtype=bool)
+        assert (deg[ordinary & ~sink] == 1).all() and (deg[sink] == 0).all() and (deg[sc.ISOLATED] == 0).all()
+        assert not np.isin(cg.col, sc.ISOLATED).any()                        # isolated: no edge in either
+        assert np.isin(cg.col, np.flatnonzero(deg == 0)).any() == sinks      # only the sink variant has a reachable sink
+        for r, row in enumerate(sc.ROWS):
+            lo, hi = cg.rowptr[sc.START0 + 2 * r], cg.rowptr[sc.START0 + 2 * r + 1]
+            assert np.array_equal(cg.col[lo:hi], row) and np.unique(row).size == row.size
+            assert np.allclose(np.diff(np.concatenate([[0.0], cg.cdf[lo:hi]])), 1.0 / row.size, rtol=1e-9)       # equal weights
+    assert sc.V <= 300_000 and deg[0] == 1 and deg[sc.V - 1] == 1
+
+
+def test_the_table_covers_the_shapes_and_every_slot_count():
+    cases = list(sc.CASES.values())
+    assert {c.P for c in cases} == LISTED_P | {200} | {193, 449, 961, 1985, 4033}         # the reference's 100 x 2; 64 NP - 63 for NP > 2
+    assert any((c.W, c.L) == (100, 2) for c in cases) and {c.L for c in cases} >= {1, 2, 3, 4}
+    for n in (1, 2, 4, 8, 16, 32, 64):                                       # every NP the launcher instantiates
+        mine = [c for c in cases if sc.n_slots(c.P) == n]
+        assert any(c.P == 64 * n for c in mine), n                           # the position buffer exactly full
+        assert any(c.P == 64 * n - 63 for c in mine), n                      # only lane 0 of the last slot
+    assert {257, 1025} <= {c.P for c in cases if c.want.get("lane0")}        # ... and of a middle slot, the later ones unused
+    for c in cases:
+        assert 1 in sc.case_T(c) and c.P in sc.case_T(c) and max(sc.case_T(c)) > c.P, c.name
+        if c.P in (51, 102, 204, 409, 819, 1638, 3276):                      # 1.25 P just fits: one slot more would not
+            assert (1 << sc.hs_log2(c.P)) * 4 - 5 * c.P < 5
+
+
+_CHECKS = {"wrap": lambda k, v: k["wrap"], "bit0": lambda k, v: k["bit0"] == v, "hole": lambda k, v: k["hole"],
+           "all_die": lambda k, v: k["all_die"], "returns": lambda k, v: k["returns"], "full": lambda k, v: k["full"],
+           "lane0": lambda k, v: k["lane0"], "last_slot": lambda k, v: k["last_slot"], "chain": lambda k, v: k["chain"] >= v, "load": lambda k, v: k["load"] > v,
+           "maxcount": lambda k, v: k["maxcount"] == v, "slots_used": lambda k, v: k["slots_used"] == v,
+           "words": lambda k, v: v <= k["words"], "has_ids": lambda k, v: set(v) <= k["ids"], "order": lambda k, v: set(v) <= k["order"]}
+
+
+@pytest.mark.parametrize("name", list(sc.CASES))
+def test_case_reaches_what_it_is_named_for(name):
+    c = sc.CASES[name]
+    k = sc.classify(c)
+    cuts = [i for i in (sc.cut_info(c, T) for T in sc.case_T(c)) if i is not None]
+    for what, v in c.want.items():
+        if what == "cut_slots":
+            assert any(len(slots) >= v for _, slots, _ in cuts), (name, what)
+        elif what == "cut_same_slot":
+            assert any(same for _, _, same in cuts), (name, what)
+        else:
+            assert _CHECKS[what](k, v), (name, what, v)
+    if c.cuts == "all":                                                      # every position of every tie class is a T
+        r, count = k["ranked"], k["count"]
+        assert all(T in sc.case_T(c) for T in range(1, len(r)) if count[r[T - 1]] == count[r[T]])
+
+
+def test_the_situations_of_the_list_are_all_there():
+    ks = {n: sc.classify(c) for n, c in sc.CASES.items()}
+    counts = set().union(*[set(k["count"].values()) for k in ks.values()])
+    assert {31, 32, 33, 63, 64, 65, 1023, 1024, 1025, 2048, 4096} <= counts
+    assert ks["one_1024"]["P"] == 1024 and ks["one_1024"]["words"] == {32}   # word 32 of the fixed 40-word bitmap
+    assert max(max(k["words"]) for k in ks.values()) == 128 and any(k["P"] > 1024 and 32 < max(k["words"]) < 128 for k in ks.values())
+    assert all(any(c.want.get("order") and o in ks[n]["order"] for n, c in sc.CASES.items()) for o in ("id", "last", "lane", "hash"))
+    # a class cut between two members of one ballot, and between members of two position slots
+    kinds = set()
+    for c in sc.CASES.values():
+        k = ks[c.name]
+        for T in sc.case_T(c):
+            i = sc.cut_info(c, T)
+            if i is not None:
+                kinds.add((len(i[1]) > 1, i[2]))
+    assert kinds == {(False, True), (True, True), (True, False)}
+    for T in (63, 64, 65, 100):                                              # above 64, below the number of distinct nodes
+        assert any(T in sc.case_T(c) and ks[c.name]["distinct"] > 100 for c in sc.CASES.values())
+    sinks = [c for c in sc.CASES.values() if c.sinks]
+    assert any(ks[c.name]["all_die"] for c in sinks) and any(ks[c.name]["hole"] and not ks[c.name]["all_die"] for c in sinks)
+    assert any(ks[c.name]["returns"] for c in sc.CASES.values() if not c.sinks)
+    for prefix in sc.FUSED.values():                                         # heavy collisions, then one node, then all distinct
+        assert ks[prefix + "_heavy"]["chain"] >= 32 and ks[prefix + "_one"]["distinct"] <= 2 and ks[prefix + "_distinct"]["maxcount"] == 1
+        assert len({sc.CASES[prefix + s].row for s in ("_heavy", "_one", "_distinct")}) == 1
+
+
+def _nodes(cases):
+    return np.asarray([c.start for c in cases], dtype=np.int64)
+
+
+@pytest.mark.parametrize("W,L,sinks", sc.SHAPES)
+def test_restatement_equals_the_c_oracle_at_every_T(W, L, sinks):
+    cases = sc.shape_cases(W, L, sinks)
+    P = W * L
+    full = sc.expected_batch(cases, P)
+    for c in cases:                                                          # the walk is np.searchsorted's; the position-buffer form agrees
+        p = sc.plant(c)
+        assert sc.select(p.pos, c.start, P) == sc.expected(c, P) and sc.select(p.pos, c.start, 1) == sc.expected(c, 1), c.name
+    for T in sc.shape_T(W, L, sinks):
+        want = sc.expected_batch(cases, T)
+        o = sc.oracle_batch(cases, _nodes(cases), T, sinks)
+        for i, c in enumerate(cases):
+            assert np.array_equal(o[0][i], want[0][i]) and np.array_equal(o[1][i], want[1][i]) and o[2][i] == want[2][i], (c.name, T)
+        n = min(T, P)
+        assert np.array_equal(want[0][:, :n], full[0][:, :n]) and np.array_equal(want[1][:, :n], full[1][:, :n])
+        assert (want[0][:, P:] == -1).all() and (want[1][:, P:] == 0).all() and np.array_equal(want[2], np.minimum(full[2], T))
+
+
+# the case each slip is shown on (any other it changes is printed)
+SLIP_SHOWN_ON = {"by_id": "shuffle_256", "by_last_visit": "shuffle_128", "lane_major": "distinct_65", "ascending": "c31_32_33",
+                 "bit0_dropped": "one_1024", "saturate_1023": "c2048_1025_1023", "start_excluded": "ref_return",
+                 "hole_ends": "sink_mixed_68x3", "pad_count": "c1024_1", "nvalid_unclamped": "tight_51_collide"}
+
+
+def test_every_slip_changes_a_named_case():
+    assert set(SLIP_SHOWN_ON) == set(sc.SLIPS)
+    for slip in sc.SLIPS:
+        hit = []
+        for c in sc.CASES.values():
+            p = sc.plant(c)
+            if any(sc.select(p.pos, c.start, T, slip) != sc.expected(c, T) for T in (1, c.P, c.P + 7)):
+                hit.append(c.name)
+        print(f"{slip}: changes {len(hit)} cases: {' '.join(hit)}")
+        assert SLIP_SHOWN_ON[slip] in hit, (slip, hit)
+
+
+def test_the_restated_constants_still_stand_in_the_kernel():
+    """plain text search: a change to the kernel's table arithmetic flags helpers/select_cases.py as stale"""
+    src = open(os.path.join(HERE, "..", "movie-recommendation-engine_amd", "csrc", "walk_sample.hip")).read()
+    for text in (f"* {sc.HASH_MULT}u) >> (32 - a.hs_log2)", "int hs_log2 = 6;", "(1 << hs_log2) * 4 < 5 * P", "(P >> 5) + 1",
+                 f"P > {sc.MAX_P}", "(h + 1) & (uint32_t)(HS - 1)", "const int p = j * 64 + lane;", "cr[j] >> 5], 1u << (cr[j] & 31)",
+                 "while (np * 64 < P) np <<= 1;"):
+        assert text in src, text
+    assert (sc.hs_log2(51), sc.hs_log2(52), sc.hs_log2(3276), sc.hs_log2(3277), sc.hs_log2(4096)) == (6, 7, 12, 13, 13)
+    assert sc.SLOTS == 64 and sc.bitmap_words(1024) == 33 <= int(re.search(r"BITMAP_WORDS = (\d+);", src).group(1))
+
+
+def _reach(counts_full, T):
+    """(highest count, counts on a bitmap word boundary, the largest class a cut at T divides) of full histograms [B, P]"""
+    c = np.asarray(counts_full)
+    edge = sorted(set(c[(c >= 32) & (c % 32 == 0)].tolist()))
+    cut = 0
+    if T < c.shape[1]:
+        divided = (c[:, T] > 0) & (c[:, T] == c[:, T - 1])
+        cut = int(((c == c[:, T:T + 1]) & divided[:, None]).sum(axis=1).max())
+    return int(c.max()), edge, cut
+
+
+def test_what_the_earlier_sampler_cases_reach():
+    """The figures DESIGN.md §2 quotes.  The seeded cases of test_sampler_vs_c_oracle_seeded count no node more than 27 times, so
+    they never leave word 0 of the bitmap, but their T does cut tie classes (of up to 154 singles).  The walk_cases batches DO
+    reach counts on word boundaries (32 and 64 at (100, 2); up to 192 at (192, 3), highest count 201: rows of one or two edges
+    collect the walks) -- by the way, not by plan -- and ask for T = W * L, so no class is ever cut there."""
+    from conftest import bipartite_graph
+    from oracle import c_oracle as co
+    ei, ew = bipartite_graph(2000, 1500, 120000, 3, "half")
+    cg = co.Graph(ei, ew, threads=4)
+    nodes = np.arange(2000)
+    seen = {}
+    for W, L, T in [(100, 2, 10), (100, 2, 50), (64, 1, 5), (33, 5, 7), (200, 3, 20), (1, 1, 1)]:
+        uoff, n = cg.uniform_offsets(nodes, W, L)
+        u = np.random.RandomState(42).random_sample(n)
+        seen[("seeded", W, L, T)] = _reach(co.walk_sample(cg, nodes, W * L, L, W, uniforms=u, uoff=uoff, threads=4)[1], T)
+    for W, L in wc.SHAPES:
+        seen[("planted", W, L, W * L)] = _reach(wc.planted_batch(W, L)[2].histogram(W * L)[1], W * L)
+    for k, v in seen.items():
+        print(k, "highest count %d, word-boundary counts %s, largest class cut %d" % v)
+    REACH = {("seeded", 100, 2, 10): (16, [], 27), ("seeded", 100, 2, 50): (16, [], 129), ("seeded", 64, 1, 5): (12, [], 21),
+             ("seeded", 33, 5, 7): (8, [], 154), ("seeded", 200, 3, 20): (27, [], 23), ("seeded", 1, 1, 1): (1, [], 0),
+             ("planted", 100, 2, 200): (100, [32, 64], 0), ("planted", 192, 3, 576): (201, [32, 64, 96, 128, 192], 0),
+             ("planted", 1, 1, 1): (1, [], 0)}
+    assert seen == REACH
