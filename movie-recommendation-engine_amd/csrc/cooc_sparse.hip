@@ -266,12 +266,10 @@ extern "C" int ps_cooc_pairs_sparse(const int64_t *iptr, const int32_t *iuser, c
     const size_t lds = lds_bytes(S);
     static PsPerDevice cus;                                           // attribute set, CU count known
     int dv = 0;
-    if (hipGetDevice(&dv) != hipSuccess || dv < 0 || dv >= 64) return PS_ELAUNCH;
+    if (!ps_device_index(&dv)) return PS_ELAUNCH;
     int ncu = cus.get(dv);
     if (ncu == 0) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(cooc_sparse_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess)
-            return PS_ELAUNCH;
+        if (!ps_allow_lds(cooc_sparse_kernel, 160 * 1024)) return PS_ELAUNCH;
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dv) != hipSuccess || ncu <= 0) return PS_ELAUNCH;
         cus.set(dv, ncu);
     }

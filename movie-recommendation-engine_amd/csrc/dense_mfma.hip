@@ -176,10 +176,11 @@ __device__ __forceinline__ float transpose_sum32(float (&v)[NV], int lane) {
 
 // One (row, 8-k group) item, registers lo = k 0..3, hi = k 4..7, into its LDS image [lane half h][4] = k 2 t + h.
 // (Writing the permutation with ds_write2_b32 from two unrelated registers needs no moves at all but measured equal: its
-// 8-byte writes conflict 4-way.)
+// 8-byte writes conflict 4-way.)  The empty asm pins the permuting register moves HERE, after the barrier: left to itself the
+// compiler performs them right behind the loads, i.e. waits for global memory inside the MFMA stream of the previous step
 template <bool PIN>
 __device__ __forceinline__ void stash_item(float *d, f32x4 lo, f32x4 hi) {
-    if (PIN) asm volatile("" : "+v"(lo), "+v"(hi));  // pins the moves behind the barrier (else: vmcnt waits among the MFMAs)
+    if (PIN) asm volatile("" : "+v"(lo), "+v"(hi));
     *reinterpret_cast<f32x4 *>(d) = f32x4{lo[0], lo[2], hi[0], hi[2]};
     *reinterpret_cast<f32x4 *>(d + 4) = f32x4{lo[1], lo[3], hi[1], hi[3]};
 }
@@ -194,9 +195,94 @@ __device__ __forceinline__ void stash_item_stored(float *d, f32x4 lo, f32x4 hi) 
     *reinterpret_cast<f32x4 *>(d + 4) = hi;
 }
 
-// FAST: every operand is 16-B aligned with K % BK == 0 -> unconditional float4 loads (rows past the end are
-// clamped to the last valid row; their results are never stored), so nothing branches or waits inside the
-// fetch and the loads stay in flight under the MFMAs.  The general variant predicates every element.
+// ------------------------------------------------------------------------------------------------------------
+// The register-staged block tile of gemm_f32_kernel and gemm_f32_pkernel: its constants, its LDS carve-up (floats from the base:
+// the image of A at 0, of B at OFF_B, the epilogue's row sums and norms behind them), and below the three things a K step is
+// made of -- the aligned fetch of the next slab into registers, the stash of the registers into the LDS image, the MFMA step.
+template <int WM_, int WN_, int TM_, int TN_, int BK>
+struct GemmTile {
+    static constexpr int WM = WM_, WN = WN_, TM = TM_, TN = TN_;
+    static constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NT = WM * WN * 64;
+    static constexpr int GRP = BK / 8;                        // 8-k groups per row
+    static constexpr int LDS_STRIDE = BK + 4;                 // floats; 144 B (BK 32) / 80 B (BK 16): b128 reads conflict free
+    static constexpr int A_ITEMS = (BM * GRP + NT - 1) / NT, B_ITEMS = (BN * GRP + NT - 1) / NT;   // (row, group) items per thread
+    static constexpr int OFF_B = BM * LDS_STRIDE, OFF_RED = (BM + BN) * LDS_STRIDE, OFF_NRM = OFF_RED + BM * WN;
+    static constexpr int LDS_FLOATS = OFF_NRM + BM * 4;
+};
+
+// Aligned load of one item (FAST: every operand is 16-B aligned with K % BK == 0): unconditional float4 loads, two per item, so
+// nothing branches or waits inside the fetch and the loads stay in flight under the MFMAs.  `row` is the caller's: rows past the
+// end are clamped to the last valid row (their results are never stored); the layer GEMM reads x through its row order.
+__device__ __forceinline__ void load_item(const float *base, int64_t row, int ld, int k0, int grp, f32x4 (&r)[2]) {
+    const float *src = base + row * ld + k0 + grp * 8;
+    r[0] = *reinterpret_cast<const f32x4 *>(src);
+    r[1] = *reinterpret_cast<const f32x4 *>(src + 4);
+}
+// The stash of this thread's items of a ROWS-row operand tile into the operand's LDS image; `stored`: the operand is stored in
+// image order (block-uniform).  No guards: when the tile has fewer items than threads the surplus threads duplicate an item
+// (identical loads, identical LDS writes) -- except with GUARD (the general path, which predicates every element): they skip.
+template <typename T, int ROWS, bool PIN, bool GUARD, int ITEMS>
+__device__ __forceinline__ void stash_items(int tid, float *img, const f32x4 (&r)[ITEMS][2], bool stored) {
+#pragma unroll
+    for (int q = 0; q < ITEMS; ++q) {
+        const int it = GUARD ? tid + T::NT * q : (tid + T::NT * q) % (ROWS * T::GRP);
+        const int row = it / T::GRP, grp = it % T::GRP;
+        if (GUARD && it >= ROWS * T::GRP) continue;
+        float *d = img + row * T::LDS_STRIDE + grp * 8;
+        if (stored) stash_item_stored<PIN>(d, r[q][0], r[q][1]);
+        else stash_item<PIN>(d, r[q][0], r[q][1]);
+    }
+}
+
+// One K step of a wave on the published image: BK / 8 groups of 4 TM TN v_mfma_f32_32x32x2_f32.
+// Fragments of group g+1 are requested BEFORE group g's MFMAs: the two waves of a SIMD run in lockstep (same barriers,
+// round-robin issue), so an LDS round trip taken between groups idles the MFMA pipe for both of them -- measured 65 % pipe use
+// without this prefetch.  The compiler otherwise sinks the reads behind the MFMAs, so the issue order of the step (one basic
+// block) is pinned with sched_group_barrier.  SPREAD: the global loads of the next K step, which the caller requests right
+// before the step, are spread over the MFMAs, one after every TM*TN of them: issued in one burst after the barrier they kept all
+// eight waves of the CU in the address path while the MFMA pipe idled (knock-out: 22 of 176 us).  That pays for the 2 x 2-tile
+// waves (10 loads per 64 MFMAs); the 1 x 2-tile blocks measured 3 % slower with it (LSH projection 0.151 -> 0.155 ms).  With
+// SPREAD the caller's fetch is therefore unconditional (the last step re-reads a slab it has: harmless), so that the loads, the
+// fragment reads and the MFMAs of a step are ONE basic block and the pinned order applies to all of them.
+// first: the first step of a contraction (PS_GEMM_DEBUG & 16 reads fragments then only).
+template <typename T, bool SPREAD>
+__device__ __forceinline__ void gemm_step(const float *sA, const float *sB, int wm, int wn, int li, int lh, bool first,
+                                          f32x16 (&acc)[T::TM][T::TN]) {
+    constexpr int TM = T::TM, TN = T::TN, GRP = T::GRP, LDS_STRIDE = T::LDS_STRIDE;
+    f32x4 fa[2][TM], fb[2][TN];
+    auto frags = [&](int grp, int s) __attribute__((always_inline)) {
+#pragma unroll
+        for (int a = 0; a < TM; ++a)
+            fa[s][a] = *reinterpret_cast<const f32x4 *>(sA + ((wm * TM + a) * 32 + li) * LDS_STRIDE + grp * 8 + lh * 4);
+#pragma unroll
+        for (int b = 0; b < TN; ++b)
+            fb[s][b] = *reinterpret_cast<const f32x4 *>(sB + ((wn * TN + b) * 32 + li) * LDS_STRIDE + grp * 8 + lh * 4);
+    };
+    if (!(PS_GEMM_DEBUG & 16) || first) frags(0, 0);
+#pragma unroll
+    for (int grp = 0; grp < GRP; ++grp) {
+        const int s = (PS_GEMM_DEBUG & 16) ? 0 : grp & 1;
+        if (grp + 1 < GRP && !(PS_GEMM_DEBUG & 16)) frags(grp + 1, s ^ 1);
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int a = 0; a < TM; ++a)
+#pragma unroll
+                for (int b = 0; b < TN; ++b)
+                    acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[s][a][t], fb[s][b][t], acc[a][b], 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, 0);
+#pragma unroll
+    for (int grp = 0; grp < GRP; ++grp) {
+        if (grp + 1 < GRP) __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, 0);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            __builtin_amdgcn_sched_group_barrier(0x008, TM * TN, 0);
+            if (SPREAD) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+        }
+    }
+}
+
 // The epilogue of a block tile (bias / ReLU / fused row L2 norm / stores, or the LSH sign + ballot bit-pack), shared by the one-tile
 // kernel and the persistent kernel below.  C layout (32x32 tile): col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5).
 // PERM (ps_gcn_layer): tile row rowl is output row sOrd[rowl].
@@ -452,16 +538,12 @@ template <int WM, int WN, int TM, int TN, int BK, int EPI, bool FAST, int GCN = 
 #endif
 __global__ __launch_bounds__(WM * WN * 64, PS_GEMM_OCC) void gemm_f32_kernel(GemmArgs g_in) {
     GemmArgs g = g_in;
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NT = WM * WN * 64;
-    // global loads of the next K step spread over the MFMAs (below): pays for the 2 x 2-tile waves (10 loads per 64 MFMAs);
-    // the 1 x 2-tile blocks measured 3 % slower with it (LSH projection 0.151 -> 0.155 ms)
-    constexpr bool SPREAD = FAST && PS_GEMM_SPREAD && TM * TN >= 4;
-    constexpr int GRP = BK / 8;                        // 8-k groups per row
-    constexpr int LDS_STRIDE = BK + 4;                 // floats; 144 B (BK 32) / 80 B (BK 16): b128 reads conflict free
-    constexpr int A_ITEMS = (BM * GRP + NT - 1) / NT, B_ITEMS = (BN * GRP + NT - 1) / NT;   // (row, group) items per thread
-    __shared__ __attribute__((aligned(16))) float smem[(BM + BN) * LDS_STRIDE + BM * WN + BM * 4 + (GCN ? BM : 0)];
-    float *sA = smem, *sB = smem + BM * LDS_STRIDE, *sRed = smem + (BM + BN) * LDS_STRIDE, *sNrm = sRed + BM * WN;
-    int *sOrd = reinterpret_cast<int *>(sNrm + BM * 4);
+    using T = GemmTile<WM, WN, TM, TN, BK>;
+    constexpr int BM = T::BM, BN = T::BN, NT = T::NT, GRP = T::GRP, A_ITEMS = T::A_ITEMS, B_ITEMS = T::B_ITEMS;
+    constexpr bool SPREAD = FAST && PS_GEMM_SPREAD && TM * TN >= 4;                    // see gemm_step
+    __shared__ __attribute__((aligned(16))) float smem[T::LDS_FLOATS + (GCN ? BM : 0)];
+    float *sA = smem, *sB = smem + T::OFF_B, *sRed = smem + T::OFF_RED, *sNrm = smem + T::OFF_NRM;
+    int *sOrd = reinterpret_cast<int *>(smem + T::LDS_FLOATS);
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int wm = wv / WN, wn = wv % WN;
@@ -537,16 +619,13 @@ __global__ __launch_bounds__(WM * WN * 64, PS_GEMM_OCC) void gemm_f32_kernel(Gem
         auto fetch = [&](int k0) {
 #pragma unroll
             for (int q = 0; q < A_ITEMS; ++q) {
-                // FAST: no guards -- when the tile has fewer items than threads the surplus threads duplicate an
-                // item (identical loads, identical LDS writes)
+                // FAST: no guards, surplus threads duplicate an item (stash_items)
                 const int it = FAST ? (tid + NT * q) % (BM * GRP) : tid + NT * q, row = it / GRP, grp = it % GRP;
                 const int64_t m = m0 + row;
                 if (FAST) {
                     int64_t srow = m < g.M ? m : g.M - 1;
                     if constexpr (GCN > 0) srow = phase == 0 ? xrow[q] : srow - m0;     // x through the order; the slab by tile row
-                    const float *src = X + srow * K + k0 + grp * 8;
-                    ra[q][0] = *reinterpret_cast<const f32x4 *>(src);
-                    ra[q][1] = *reinterpret_cast<const f32x4 *>(src + 4);
+                    load_item(X, srow, K, k0, grp, ra[q]);
                 } else if (it < BM * GRP) {
                     float v[8];
                     load8(X + m * K, m < g.M, k0 + grp * 8, K, vecA, v);
@@ -559,9 +638,7 @@ __global__ __launch_bounds__(WM * WN * 64, PS_GEMM_OCC) void gemm_f32_kernel(Gem
                 const int it = FAST ? (tid + NT * q) % (BN * GRP) : tid + NT * q, row = it / GRP, grp = it % GRP;
                 const int n = n0 + row;
                 if (FAST) {
-                    const float *src = Wp + (int64_t)(n < g.N ? n : g.N - 1) * ldw + k0 + grp * 8;
-                    rb[q][0] = *reinterpret_cast<const f32x4 *>(src);
-                    rb[q][1] = *reinterpret_cast<const f32x4 *>(src + 4);
+                    load_item(Wp, n < g.N ? n : g.N - 1, ldw, k0, grp, rb[q]);
                 } else if (it < BN * GRP) {
                     float v[8];
                     load8(Wp + (int64_t)n * ldw, n < g.N, k0 + grp * 8, K, vecB, v);
@@ -570,25 +647,9 @@ __global__ __launch_bounds__(WM * WN * 64, PS_GEMM_OCC) void gemm_f32_kernel(Gem
                 }
             }
         };
-        // LDS image of an item: [lane half h][4] = k 2 t + h.  The empty asm pins the permuting register moves HERE, after
-        // the barrier: left to itself the compiler performs them right behind the loads, i.e. waits for global memory
-        // inside the MFMA stream of the previous step
         auto stash = [&]() {
-#pragma unroll
-            for (int q = 0; q < A_ITEMS; ++q) {
-                const int it = FAST ? (tid + NT * q) % (BM * GRP) : tid + NT * q, row = it / GRP, grp = it % GRP;
-                if (!FAST && it >= BM * GRP) continue;
-                float *d = sA + row * LDS_STRIDE + grp * 8;
-                stash_item<SPREAD>(d, ra[q][0], ra[q][1]);
-            }
-#pragma unroll
-            for (int q = 0; q < B_ITEMS; ++q) {
-                const int it = FAST ? (tid + NT * q) % (BN * GRP) : tid + NT * q, row = it / GRP, grp = it % GRP;
-                if (!FAST && it >= BN * GRP) continue;
-                float *d = sB + row * LDS_STRIDE + grp * 8;
-                if (FAST && wperm) stash_item_stored<SPREAD>(d, rb[q][0], rb[q][1]);
-                else stash_item<SPREAD>(d, rb[q][0], rb[q][1]);
-            }
+            stash_items<T, BM, SPREAD, !FAST>(tid, sA, ra, false);
+            stash_items<T, BN, SPREAD, !FAST>(tid, sB, rb, FAST && wperm);
         };
 
         fetch(0);
@@ -603,49 +664,9 @@ __global__ __launch_bounds__(WM * WN * 64, PS_GEMM_OCC) void gemm_f32_kernel(Gem
             PS_TRACE(3 + 2 * trace_step);                                   // image published: MFMA stream starts
             ++trace_step;
 #endif
-            // FAST: unconditional (the last step re-reads its own slab: harmless) so that the loads, the fragment reads and
-            // the MFMAs of a step are ONE basic block and the issue order below applies to all of them
-            if (SPREAD && !(PS_GEMM_DEBUG & 1)) fetch(k0 + BK < K ? k0 + BK : k0);
+            if (SPREAD && !(PS_GEMM_DEBUG & 1)) fetch(k0 + BK < K ? k0 + BK : k0);        // unconditional: see gemm_step
             else if (k0 + BK < K && !(PS_GEMM_DEBUG & 1)) fetch(k0 + BK);
-            // fragments of group g+1 are requested BEFORE group g's MFMAs: the two waves of a SIMD run in lockstep
-            // (same barriers, round-robin issue), so an LDS round trip taken between groups idles the MFMA pipe for
-            // both of them -- measured 65 % pipe use without this prefetch
-            f32x4 fa[2][TM], fb[2][TN];
-            auto frags = [&](int grp, int s) {
-#pragma unroll
-                for (int a = 0; a < TM; ++a)
-                    fa[s][a] = *reinterpret_cast<const f32x4 *>(sA + ((wm * TM + a) * 32 + li) * LDS_STRIDE + grp * 8 + lh * 4);
-#pragma unroll
-                for (int b = 0; b < TN; ++b)
-                    fb[s][b] = *reinterpret_cast<const f32x4 *>(sB + ((wn * TN + b) * 32 + li) * LDS_STRIDE + grp * 8 + lh * 4);
-            };
-            if (!(PS_GEMM_DEBUG & 16) || k0 == 0) frags(0, 0);
-#pragma unroll
-            for (int grp = 0; grp < GRP; ++grp) {
-                const int s = (PS_GEMM_DEBUG & 16) ? 0 : grp & 1;
-                if (grp + 1 < GRP && !(PS_GEMM_DEBUG & 16)) frags(grp + 1, s ^ 1);
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int a = 0; a < TM; ++a)
-#pragma unroll
-                        for (int b = 0; b < TN; ++b)
-                            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[s][a][t], fb[s][b][t], acc[a][b], 0, 0, 0);
-            }
-            // issue order of the step (one basic block): the fragments of group g+1 are requested BEFORE group g's MFMAs
-            // (the compiler otherwise sinks the reads behind them), and the global loads of the next K step are spread
-            // over the MFMAs, one after every TM*TN of them: issued in one burst after the barrier they kept all eight
-            // waves of the CU in the address path while the MFMA pipe idled (knock-out: 22 of 176 us)
-            __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, 0);
-#pragma unroll
-            for (int grp = 0; grp < GRP; ++grp) {
-                if (grp + 1 < GRP) __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, 0);
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, TM * TN, 0);
-                    if (SPREAD) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                }
-            }
+            gemm_step<T, SPREAD>(sA, sB, wm, wn, li, lh, k0 == 0, acc);
         }
     }
 
@@ -661,13 +682,11 @@ __global__ __launch_bounds__(WM * WN * 64, PS_GEMM_OCC) void gemm_f32_kernel(Gem
 // accumulator per output, k ascending.
 template <int WM, int WN, int TM, int TN, int BK, int EPI>
 __global__ __launch_bounds__(WM * WN * 64, PS_GEMM_OCC) void gemm_f32_pkernel(GemmArgs g, int tiles_n, int ntiles) {
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NT = WM * WN * 64;
+    using T = GemmTile<WM, WN, TM, TN, BK>;
+    constexpr int BM = T::BM, BN = T::BN, NT = T::NT, GRP = T::GRP, A_ITEMS = T::A_ITEMS, B_ITEMS = T::B_ITEMS;
     constexpr bool SPREAD = PS_GEMM_SPREAD && TM * TN >= 4;
-    constexpr int GRP = BK / 8;
-    constexpr int LDS_STRIDE = BK + 4;
-    constexpr int A_ITEMS = (BM * GRP + NT - 1) / NT, B_ITEMS = (BN * GRP + NT - 1) / NT;
-    __shared__ __attribute__((aligned(16))) float smem[(BM + BN) * LDS_STRIDE + BM * WN + BM * 4];
-    float *sA = smem, *sB = smem + BM * LDS_STRIDE, *sRed = smem + (BM + BN) * LDS_STRIDE, *sNrm = sRed + BM * WN;
+    __shared__ __attribute__((aligned(16))) float smem[T::LDS_FLOATS];
+    float *sA = smem, *sB = smem + T::OFF_B, *sRed = smem + T::OFF_RED, *sNrm = smem + T::OFF_NRM;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int wm = wv / WN, wn = wv % WN;
     const int li = lane & 31, lh = lane >> 5;
@@ -686,31 +705,19 @@ __global__ __launch_bounds__(WM * WN * 64, PS_GEMM_OCC) void gemm_f32_pkernel(Ge
         for (int q = 0; q < A_ITEMS; ++q) {
             const int it = (tid + NT * q) % (BM * GRP), row = it / GRP, grp = it % GRP;
             const int64_t m = m0 + row;
-            const float *src = X + (m < g.M ? m : g.M - 1) * K + k0 + grp * 8;
-            ra[q][0] = *reinterpret_cast<const f32x4 *>(src);
-            ra[q][1] = *reinterpret_cast<const f32x4 *>(src + 4);
+            load_item(X, m < g.M ? m : g.M - 1, K, k0, grp, ra[q]);
         }
 #pragma unroll
         for (int q = 0; q < B_ITEMS; ++q) {
             const int it = (tid + NT * q) % (BN * GRP), row = it / GRP, grp = it % GRP;
             const int n = n0 + row;
-            const float *src = Wp + (int64_t)(n < g.N ? n : g.N - 1) * ldw + k0 + grp * 8;
-            rb[q][0] = *reinterpret_cast<const f32x4 *>(src);
-            rb[q][1] = *reinterpret_cast<const f32x4 *>(src + 4);
+            load_item(Wp, n < g.N ? n : g.N - 1, ldw, k0, grp, rb[q]);
         }
     };
+    // (a lambda, like fetch: with the two calls written into the loop the compiler orders the kernel's instructions differently)
     auto stash = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int q = 0; q < A_ITEMS; ++q) {
-            const int it = (tid + NT * q) % (BM * GRP), row = it / GRP, grp = it % GRP;
-            stash_item<SPREAD>(sA + row * LDS_STRIDE + grp * 8, ra[q][0], ra[q][1]);
-        }
-#pragma unroll
-        for (int q = 0; q < B_ITEMS; ++q) {
-            const int it = (tid + NT * q) % (BN * GRP), row = it / GRP, grp = it % GRP;
-            if (wperm) stash_item_stored<SPREAD>(sB + row * LDS_STRIDE + grp * 8, rb[q][0], rb[q][1]);
-            else stash_item<SPREAD>(sB + row * LDS_STRIDE + grp * 8, rb[q][0], rb[q][1]);
-        }
+        stash_items<T, BM, SPREAD, false>(tid, sA, ra, false);
+        stash_items<T, BN, SPREAD, false>(tid, sB, rb, wperm);
     };
 
     int tile = blockIdx.x;
@@ -735,43 +742,12 @@ __global__ __launch_bounds__(WM * WN * 64, PS_GEMM_OCC) void gemm_f32_pkernel(Ge
             stash();
             __syncthreads();
             // the next slab: of this tile, or the first one of the workgroup's next tile, or (nothing left) this one again --
-            // always a fetch, so that the loads, the fragment reads and the MFMAs of a step are ONE basic block
+            // always a fetch (see gemm_step)
             {
                 const bool last = s + 1 >= nsteps;
                 fetch(last ? m0n : m0, last ? n0n : n0, last ? (more ? 0 : s) : s + 1);
             }
-            f32x4 fa[2][TM], fb[2][TN];
-            auto frags = [&](int grp, int sl) __attribute__((always_inline)) {
-#pragma unroll
-                for (int a = 0; a < TM; ++a)
-                    fa[sl][a] = *reinterpret_cast<const f32x4 *>(sA + ((wm * TM + a) * 32 + li) * LDS_STRIDE + grp * 8 + lh * 4);
-#pragma unroll
-                for (int b = 0; b < TN; ++b)
-                    fb[sl][b] = *reinterpret_cast<const f32x4 *>(sB + ((wn * TN + b) * 32 + li) * LDS_STRIDE + grp * 8 + lh * 4);
-            };
-            frags(0, 0);
-#pragma unroll
-            for (int grp = 0; grp < GRP; ++grp) {
-                const int sl = grp & 1;
-                if (grp + 1 < GRP) frags(grp + 1, sl ^ 1);
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int a = 0; a < TM; ++a)
-#pragma unroll
-                        for (int b = 0; b < TN; ++b)
-                            acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[sl][a][t], fb[sl][b][t], acc[a][b], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, 0);
-#pragma unroll
-            for (int grp = 0; grp < GRP; ++grp) {
-                if (grp + 1 < GRP) __builtin_amdgcn_sched_group_barrier(0x100, TM + TN, 0);
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, TM * TN, 0);
-                    if (SPREAD) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                }
-            }
+            gemm_step<T, SPREAD>(sA, sB, wm, wn, li, lh, s == 0, acc);
         }
         gemm_epilogue<WM, WN, TM, TN, EPI>(g, acc, m0, n0, sRed, sNrm);
         if (!more) break;
@@ -1193,7 +1169,7 @@ __global__ void l2norm_rows_kernel(float *y, int64_t M, int N) {   // N > 256 on
 template <typename K>
 int persistent_slots(K kernel, PsPerDevice &slots) {
     int dv = 0;
-    if (hipGetDevice(&dv) != hipSuccess || dv < 0 || dv >= 64) return 0;
+    if (!ps_device_index(&dv)) return 0;
     int n = slots.get(dv);
     if (n == 0) {
         int per_cu = 0, cus = 0;
@@ -1278,10 +1254,9 @@ int launch_shard(const GemmArgs &g, hipStream_t st) {
     constexpr int lds = STAGES * SH_STAGE_BYTES + SH_TAIL_BYTES;
     static PsPerDevice attr_done;                             // per instantiation
     int devid = 0;
-    if (hipGetDevice(&devid) != hipSuccess || devid < 0 || devid >= 64) return PS_ELAUNCH;
+    if (!ps_device_index(&devid)) return PS_ELAUNCH;
     if (!attr_done.get(devid)) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_shard_kernel<EPI, WP, STAGES>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return PS_ELAUNCH;
+        if (!ps_allow_lds(gemm_shard_kernel<EPI, WP, STAGES>, lds)) return PS_ELAUNCH;
         attr_done.set(devid, 1);
     }
     dim3 grid((unsigned)ps_cdiv(g.M, SH_BM), (unsigned)ps_cdiv(g.N, SH_BN));
@@ -1326,10 +1301,9 @@ int launch_gemm(const GemmArgs &g, hipStream_t st) {
     if (fast && use_dma && !(g.flags & PS_WPERM) && g.N % DMA_BN == 0 && g.M >= 64 * 384) {
         static PsPerDevice attr_done;
         int devid = 0;
-        if (hipGetDevice(&devid) != hipSuccess || devid < 0 || devid >= 64) return PS_ELAUNCH;
+        if (!ps_device_index(&devid)) return PS_ELAUNCH;
         if (!attr_done.get(devid)) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_dma_kernel<EPI>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    DMA_STAGES * DMA_STAGE_BYTES) != hipSuccess) return PS_ELAUNCH;
+            if (!ps_allow_lds(gemm_dma_kernel<EPI>, DMA_STAGES * DMA_STAGE_BYTES)) return PS_ELAUNCH;
             attr_done.set(devid, 1);
         }
         dim3 grid((unsigned)ps_cdiv(g.M, DMA_BM), (unsigned)(g.N / DMA_BN));

@@ -1180,13 +1180,6 @@ Plan make_plan(int64_t nq, int64_t N, int cs, int k) {
     return p;
 }
 
-// dynamic LDS beyond 64 KiB has to be allowed per kernel (idempotent; remembered per device in an atomic: PsPerDevice)
-template <typename K>
-bool allow_lds(K kernel, size_t bytes) {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) ==
-           hipSuccess;
-}
-
 // The sweep kernel of one pass (0 bound, 1 collect) and its dynamic LDS.  Two workgroups per CU (!p.db: k <= 12, 256- / 512-bit
 // codes) run the pipelined kernel, or with pipe = false its predecessor; their bound pass keeps four values per lane, so a
 // plan that wants longer lists takes its bound from the one-workgroup kernel.  nullptr: no kernel for this plan.
@@ -1217,23 +1210,23 @@ int launch_passes(const Plan &p, HArgs a, hipStream_t st, int32_t *thr0, int32_t
     // once per (kernel, device): one process may drive several GPUs
     static PsPerDevice lds_done;
     int devid = 0;
-    if (hipGetDevice(&devid) != hipSuccess || devid < 0 || devid >= 64) return PS_ELAUNCH;
+    if (!ps_device_index(&devid)) return PS_ELAUNCH;
     bool lds_ok = lds_done.get(devid) != 0;
     if (!lds_ok) {
         // the most a kernel form is ever launched with: 160 KiB at 512 bit with one workgroup per CU, 80 KiB with two
         constexpr size_t lds1 = ring_bytes<KS, true>() + column_bytes(column_cap(true, 32));
         constexpr size_t cols2 = column_bytes(column_cap(false, 12));
-        lds_ok = allow_lds(hamming_mfma_kernel<KS, 0, 4, true>, lds1) && allow_lds(hamming_mfma_kernel<KS, 0, 16, true>, lds1) &&
-                 allow_lds(hamming_mfma_kernel<KS, 1, 4, true>, lds1);
-        if constexpr (KS < 8) lds_ok = lds_ok && allow_lds(hamming_mfma_kernel<KS, 0, 32, true>, lds1);
+        lds_ok = ps_allow_lds(hamming_mfma_kernel<KS, 0, 4, true>, lds1) && ps_allow_lds(hamming_mfma_kernel<KS, 0, 16, true>, lds1) &&
+                 ps_allow_lds(hamming_mfma_kernel<KS, 1, 4, true>, lds1);
+        if constexpr (KS < 8) lds_ok = lds_ok && ps_allow_lds(hamming_mfma_kernel<KS, 0, 32, true>, lds1);
         // two workgroups per CU: 256- and 512-bit codes only (make_plan: KS <= 2 always takes the one-workgroup form, whose
         // four-tile entries do not fit 128 VGPRs -- those instantiations spilled and were never launched: not built any more)
         if constexpr (KS >= 4)
-            lds_ok = lds_ok && allow_lds(hamming_mfma_kernel<KS, 1, 4, false>, ring_bytes<KS, false>() + cols2) &&
-                     allow_lds(hamming_mfma_kernel<KS, 0, 4, false>, ring_bytes<KS, false>() + cols2);
+            lds_ok = lds_ok && ps_allow_lds(hamming_mfma_kernel<KS, 1, 4, false>, ring_bytes<KS, false>() + cols2) &&
+                     ps_allow_lds(hamming_mfma_kernel<KS, 0, 4, false>, ring_bytes<KS, false>() + cols2);
         if constexpr (PipeServed<KS>::value)
-            lds_ok = lds_ok && allow_lds(hamming_pipe_kernel<KS, 1>, pipe_ring_bytes<KS>() + cols2) &&
-                     allow_lds(hamming_pipe_kernel<KS, 0>, pipe_ring_bytes<KS>() + cols2);
+            lds_ok = lds_ok && ps_allow_lds(hamming_pipe_kernel<KS, 1>, pipe_ring_bytes<KS>() + cols2) &&
+                     ps_allow_lds(hamming_pipe_kernel<KS, 0>, pipe_ring_bytes<KS>() + cols2);
         lds_done.set(devid, lds_ok ? 1 : 0);
     }
     if (!lds_ok) return PS_ELAUNCH;

@@ -363,8 +363,7 @@ int launch_filter(const FilterArgs &g, hipStream_t st) {
 
 template <int KS, int JS>
 bool allow_lds() {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(lsh_filter_kernel<KS, JS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)filter_lds<KS, JS>(MAX_NBITS)) == hipSuccess;
+    return ps_allow_lds(lsh_filter_kernel<KS, JS>, filter_lds<KS, JS>(MAX_NBITS));
 }
 
 }  // namespace
@@ -389,7 +388,7 @@ int psi_lsh_encode_staged(const float *x, int64_t N, int D, const void *staged, 
     if (!served(nbits, D) || (reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(staged)) % 16 != 0) return PS_EUNSUPPORTED;
     static PsPerDevice cus;                                                    // attributes set, CU count known
     int dv = 0;
-    if (hipGetDevice(&dv) != hipSuccess || dv < 0 || dv >= 64) return PS_ELAUNCH;
+    if (!ps_device_index(&dv)) return PS_ELAUNCH;
     int ncu = cus.get(dv);
     if (ncu == 0) {
         if (!(allow_lds<2, 1>() && allow_lds<4, 1>() && allow_lds<8, 1>() && allow_lds<16, 1>() && allow_lds<2, 2>() &&

@@ -24,6 +24,15 @@ struct PsPerDevice {
     int get(int dev) const { return v[dev].load(std::memory_order_acquire); }
     void set(int dev, int x) { v[dev].store(x, std::memory_order_release); }
 };
+// the current device's slot of a PsPerDevice; false: no device, or one beyond the 64 slots
+static inline bool ps_device_index(int *dev) { return hipGetDevice(dev) == hipSuccess && *dev >= 0 && *dev < 64; }
+// dynamic LDS beyond 64 KiB has to be allowed per kernel and device (idempotent; every caller remembers it in a PsPerDevice of
+// its OWN: one process may drive several GPUs)
+template <typename K>
+bool ps_allow_lds(K kernel, size_t bytes) {
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) ==
+           hipSuccess;
+}
 
 static inline int64_t ps_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

@@ -777,12 +777,10 @@ static int walk_sample_launch(const int64_t *rowptr, const int32_t *col, const d
         if (lds > 64 * 1024) {                                                                                                 \
             static PsPerDevice done;                                                                                           \
             int dv = 0;                                                                                                        \
-            if (hipGetDevice(&dv) != hipSuccess || dv < 0 || dv >= 64) return PS_ELAUNCH;                                      \
+            if (!ps_device_index(&dv)) return PS_ELAUNCH;                                                                      \
             if (!done.get(dv)) {                                                                                               \
-                if (hipFuncSetAttribute(reinterpret_cast<const void *>(walk_sample_kernel<NP_, false>),                        \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||               \
-                    hipFuncSetAttribute(reinterpret_cast<const void *>(walk_sample_kernel<NP_, true>),                         \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return PS_ELAUNCH; \
+                if (!ps_allow_lds(walk_sample_kernel<NP_, false>, 160 * 1024) ||                                               \
+                    !ps_allow_lds(walk_sample_kernel<NP_, true>, 160 * 1024)) return PS_ELAUNCH;                               \
                 done.set(dv, 1);                                                                                               \
             }                                                                                                                  \
         }                                                                                                                      \
