@@ -524,6 +524,41 @@ int ps_margin_loss(const float *Q, const float *P, int64_t B, int D, const uint6
 int ps_margin_loss_bwd(const float *Q, const float *P, const float *X, int64_t B, int64_t N, int D, int mode, const int64_t *idx,
                        const uint8_t *active, const float *grad_out, float *dQ, float *dP, float *dX, ps_stream_t stream);
 
+/* ---- personalized-PageRank neighbourhoods: RandomWalkSampler.compute_ppr_matrix (utils/random_walk.py:144-195) and
+ * precompute_top_neighbors (:197-229).  All arithmetic is fp64, one rounding per product / sum / quotient, in the reference's
+ * order: scores and weights are bit-identical with the reference's python floats (csrc/ppr_push.hip has the argument).
+ *
+ * ps_ppr_shares : share[e] = wsorted[e] / sum(row), the row sum taken left to right from 0 -- `weight / sum(w for _, w in
+ *                 neighbors)` (:184).  rowptr / wsorted: ps_csr_build's; share double[E] in the same slot order.
+ * ps_ppr_push   : the push sweeps (:172-188) for S sources at once.  State is node-major: score double[Vp, Sc] (overwritten),
+ *                 Sc = S rounded up to 64, column s belongs to sources[s] (int64[S]; an id outside [0, Vp) stays all zero).
+ *                 Vp = max(V, max(sources) + 1) as the reference sizes its vectors (:159); ids >= V have no edges.
+ *                 in_rowptr int64[V+1] / in_src int32 / in_share double: the in-edges of every node IN SUMMATION ORDER -- sources
+ *                 u > v ascending, then u < v ascending, multi-edges in adjacency order, self-loops left out.
+ *                 level_nodes int32[V] + h_level_ptr int64[n_levels + 1] (HOST): the nodes grouped by
+ *                 level(v) = 1 + max level(u) over the in-neighbours u < v; one launch per level and sweep, on `stream`.
+ *                 alpha_bits: the fp64 bit pattern of alpha, 0 < alpha < 1 (the ABI carries no double scalar).
+ *                 flags: PS_PPR_NO_SKIP reads every in-edge's row instead of skipping those whose 64-source slab pushed
+ *                 nothing in that sweep (same result; for measurements).
+ * ps_ppr_topk   : the cut of :213-227 over source-major rows score double[S, ld] (ld >= Vp): per source the k best targets with
+ *                 score > 0 among ids < max_target (max_target < 0: all), score descending, ties to the smaller id.
+ *                 ids int32[S, k] (-1 pad), scores double[S, k], wts double[S, k] = score / left-to-right sum in rank order
+ *                 (0 pad), nvalid int32[S].
+ * Precondition: edge weights are positive and finite, as ratings are.  A row whose weights sum to 0 divides by zero in the
+ * reference (:184) and gives NaN shares here; negative weights give negative shares.  Neither is checked, and with such shares
+ * the row skipping of ps_ppr_push (which relies on every addend being >= +0.0) need not agree with PS_PPR_NO_SKIP.
+ * PS_EINVAL: k < 1, alpha outside (0, 1), negative sizes, unknown flags, a workspace smaller than
+ * ps_ppr_push_workspace_bytes(Vp, S), Vp * Sc / 256 beyond 2^31 workgroups; all checked before anything is enqueued. */
+#define PS_PPR_NO_SKIP 1
+int ps_ppr_shares(const int64_t *rowptr, const double *wsorted, int64_t V, double *share, ps_stream_t stream);
+size_t ps_ppr_push_workspace_bytes(int64_t Vp, int64_t S);
+int ps_ppr_push(const int64_t *in_rowptr, const int32_t *in_src, const double *in_share, int64_t V, int64_t Vp,
+                const int32_t *level_nodes, const int64_t *h_level_ptr, int n_levels, const int64_t *sources, int64_t S,
+                uint64_t alpha_bits, int sweeps, int flags, double *score, void *workspace, size_t workspace_bytes,
+                ps_stream_t stream);
+int ps_ppr_topk(const double *score, int64_t S, int64_t ld, int64_t Vp, int64_t max_target, int k, int32_t *ids, double *scores,
+                double *wts, int32_t *nvalid, ps_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

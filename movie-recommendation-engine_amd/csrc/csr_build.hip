@@ -100,18 +100,6 @@ __device__ double numpy_sum(const double *a, int64_t n) {
     return res;
 }
 
-// a / b rounded to nearest, as numpy divides.  The instruction sequence the compiler emits for an fp64 `/` is faithful
-// but not always correctly rounded: a quotient within a hair of a rounding midpoint can come out one ulp off (11 of
-// SYN-25M's 50 M CDF entries did).  q is within an ulp of a / b, so the residuals a - q b are exact (fma), and the
-// neighbour of q on the residual's side replaces q when its residual is smaller (a quotient is never exactly a midpoint).
-__device__ __forceinline__ double div_rn(double a, double b) {
-    const double q = a / b;
-    const double r = fma(-q, b, a);
-    if (r == 0.0 || !isfinite(q)) return q;
-    const double q1 = nextafter(q, ((r > 0.0) == (b > 0.0)) ? INFINITY : -INFINITY);
-    return fabs(fma(-q1, b, a)) < fabs(r) ? q1 : q;
-}
-
 constexpr int SMALL_ROW = 32;
 
 // rows with degree <= SMALL_ROW: one lane per row
@@ -122,12 +110,12 @@ __global__ void cdf_small_kernel(const int64_t *rowptr, const double *w, int64_t
         const double S = numpy_sum(w + lo, n);
         double acc = 0.0;
         for (int64_t i = lo; i < hi; ++i) {
-            const double p = div_rn(w[i], S);
+            const double p = ps_div_rn(w[i], S);
             acc = (i == lo) ? p : acc + p;
             cdf[i] = acc;
         }
         const double last = acc;
-        for (int64_t i = lo; i < hi; ++i) cdf[i] = div_rn(cdf[i], last);
+        for (int64_t i = lo; i < hi; ++i) cdf[i] = ps_div_rn(cdf[i], last);
     }
 }
 
@@ -143,7 +131,7 @@ __global__ __launch_bounds__(256) void cdf_large_kernel(const int64_t *rowptr, c
         const int64_t lo = rowptr[v], hi = rowptr[v + 1], n = hi - lo;
         if (n <= SMALL_ROW) continue;
         const double S = numpy_sum(w + lo, n);
-        for (int64_t i = lo + lane; i < hi; i += 64) cdf[i] = div_rn(w[i], S);      // p
+        for (int64_t i = lo + lane; i < hi; i += 64) cdf[i] = ps_div_rn(w[i], S);      // p
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_s_waitcnt(0);
         __builtin_amdgcn_wave_barrier();
@@ -160,7 +148,7 @@ __global__ __launch_bounds__(256) void cdf_large_kernel(const int64_t *rowptr, c
         __builtin_amdgcn_wave_barrier();
         for (int64_t i = lo + lane; i < hi; i += 64) {
             const volatile double *pc = cdf;
-            cdf[i] = div_rn(pc[i], last);
+            cdf[i] = ps_div_rn(pc[i], last);
         }
     }
 }

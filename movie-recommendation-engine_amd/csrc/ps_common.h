@@ -50,6 +50,18 @@ int psi_lsh_encode_staged(const float *x, int64_t N, int D, const void *staged, 
 
 __device__ __forceinline__ int ps_lane() { return threadIdx.x & 63; }
 
+// a / b rounded to nearest, as numpy and python divide.  The instruction sequence the compiler emits for an fp64 `/` is faithful
+// but not always correctly rounded: a quotient within a hair of a rounding midpoint can come out one ulp off (11 of
+// SYN-25M's 50 M CDF entries did).  q is within an ulp of a / b, so the residuals a - q b are exact (fma), and the
+// neighbour of q on the residual's side replaces q when its residual is smaller (a quotient is never exactly a midpoint).
+__device__ __forceinline__ double ps_div_rn(double a, double b) {
+    const double q = a / b;
+    const double r = fma(-q, b, a);
+    if (r == 0.0 || !isfinite(q)) return q;
+    const double q1 = nextafter(q, ((r > 0.0) == (b > 0.0)) ? INFINITY : -INFINITY);
+    return fabs(fma(-q1, b, a)) < fabs(r) ? q1 : q;
+}
+
 // (similarity, candidate index) as ONE unsigned word whose integer order is "larger similarity first, then smaller index":
 // high half = the float's place in its total order (-inf < ... < -0 < +0 < ... < +inf, every NaN above +inf: a NaN candidate
 // is its row's maximum, as in torch.max), low half = ~index.  Every word of a real candidate is > 0, so 0 = "no candidate",

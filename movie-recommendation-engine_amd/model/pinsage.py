@@ -132,8 +132,8 @@ def _lists_to_padded(x_rows, neighbors, weights):
 
 
 def _batch_of(neighbors, weights):
-    """The device batch behind a pair of LazyNeighborLists (or a NeighborBatch), else None."""
-    if isinstance(neighbors, sampling.NeighborBatch):
+    """The device batch behind a pair of LazyNeighborLists (or a NeighborBatch / WeightedBatch), else None."""
+    if isinstance(neighbors, (sampling.NeighborBatch, sampling.WeightedBatch)):
         return neighbors
     if isinstance(neighbors, sampling.LazyNeighborList) and isinstance(weights, sampling.LazyNeighborList) \
             and neighbors.batch is weights.batch:
@@ -152,7 +152,10 @@ class ImportancePooling(nn.Module):
         xg = x if x.is_cuda else x.to(dev)
         xg = xg.float().contiguous()
         batch = _batch_of(neighbors, weights)
-        if batch is not None:
+        if isinstance(batch, sampling.WeightedBatch):
+            # the fp64 weights rounded to fp32, as torch.tensor(python floats) rounds them on the list path (:140)
+            ids, counts, wts, nvalid = batch.ids.to(xg.device), None, batch.wts.to(xg.device, torch.float32), batch.nvalid.to(xg.device)
+        elif batch is not None:
             ids, counts, wts, nvalid = batch.ids, batch.counts, None, batch.nvalid
             if ids.device != xg.device:
                 ids, counts, nvalid = ids.to(xg.device), counts.to(xg.device), nvalid.to(xg.device)

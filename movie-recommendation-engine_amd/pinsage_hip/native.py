@@ -23,6 +23,7 @@ PS_WPERM = 4
 PS_LSH_STAGED = 8
 PS_HN_PER_QUERY, PS_HN_EXCLUDE_DIAG = 1, 2
 PS_LOSS_SHARED, PS_LOSS_PER_QUERY, PS_LOSS_BATCH_HARD = 0, 1, 2
+PS_PPR_NO_SKIP = 1
 PS_OK, PS_EINVAL, PS_ELAUNCH, PS_EWORKSPACE, PS_EUNSUPPORTED = 0, -1, -2, -3, -4      # status codes (include/pinsage_hip.h)
 
 
@@ -104,6 +105,10 @@ PROTOTYPES = {
     "ps_hardest_negative": "i pqipqipppp",
     "ps_margin_loss": "i ppqipfppppp",
     "ps_margin_loss_bwd": "i pppqqiippppppp",
+    "ps_ppr_shares": "i ppqpp",
+    "ps_ppr_push_workspace_bytes": "z qq",
+    "ps_ppr_push": "i pppqqppipqQiippzp",
+    "ps_ppr_topk": "i pqqqqippppp",
 }
 SYMBOLS = list(PROTOTYPES)
 

@@ -1,6 +1,7 @@
 """Tensor-native sampling ops over a DeviceGraph (the kernels behind RandomWalkSampler).
 
-`NeighborBatch` is the device-resident result ([B,T] ids / visit counts, [B] nvalid);
+`NeighborBatch` is the device-resident result ([B,T] ids / visit counts, [B] nvalid), `WeightedBatch` its
+counterpart with fp64 weights (personalized PageRank);
 `LazyNeighborList` is the python list-of-lists view the reference API returns
 (utils/random_walk.py:119-142), materialised only when python code actually looks at it."""
 from __future__ import annotations
@@ -47,6 +48,37 @@ class NeighborBatch:
         return nb, wt
 
 
+class WeightedBatch:
+    """ids int32[B,T] (-1 pad), wts fp64[B,T] (0 pad), nvalid int32[B] on the device: neighbourhoods that come with their
+    weights (personalized PageRank, pinsage_hip/ppr.py) instead of visit counts.  Same B / T / to_lists() as NeighborBatch,
+    so LazyNeighborList serves both.  `scores` (fp64[B,T], optional): the values the weights were normalised from."""
+
+    def __init__(self, ids, wts, nvalid):
+        self.ids, self.wts, self.nvalid = ids, wts, nvalid
+        self.scores = None
+        self._host = None
+
+    @property
+    def B(self):
+        return int(self.ids.size(0))
+
+    @property
+    def T(self):
+        return int(self.ids.size(1))
+
+    def host(self):
+        """(ids int64, wts fp64, nvalid int32) as numpy"""
+        if self._host is None:
+            self._host = (self.ids.cpu().numpy().astype(np.int64), self.wts.cpu().numpy(), self.nvalid.cpu().numpy())
+        return self._host
+
+    def to_lists(self):
+        ids, w, nvalid = self.host()
+        nb = [list(ids[i, :nvalid[i]]) for i in range(ids.shape[0])]          # np.int64 scalars
+        wt = [w[i, :nvalid[i]].tolist() for i in range(ids.shape[0])]          # python floats
+        return nb, wt
+
+
 class LazyNeighborList(list):
     """A real `list` (isinstance checks in the reference pass) whose items are produced from the
     device batch on first python-level access.  Our own kernels read `.batch` and never touch it.
@@ -56,7 +88,7 @@ class LazyNeighborList(list):
 
     EAGER_BELOW = 4096
 
-    def __init__(self, batch: NeighborBatch, kind: str):
+    def __init__(self, batch, kind: str):
         super().__init__()
         self.batch = batch
         self.kind = kind

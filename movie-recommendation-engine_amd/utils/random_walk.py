@@ -6,6 +6,7 @@ per-node loops are replaced by one kernel launch per batch:
   _prepare_adjacency_list (:33-50)      -> ps_csr_build + ps_cdf_build (CSR + fp64 CDF in HBM)
   _single_walk (:52-83)                 -> ps_walk_paths
   sample_neighbors / batch_sample_neighbors (:85-142) -> ps_walk_sample
+  compute_ppr_matrix / precompute_top_neighbors (:144-229) -> ps_ppr_shares + ps_ppr_push + ps_ppr_topk
 With rng='numpy' (default) the sampler consumes the process-global `np.random` stream exactly
 like the reference (same ids, same fp64 weights, same RNG state afterwards).
 """
@@ -105,11 +106,26 @@ class RandomWalkSampler:
         batch = self.sample_batch(nodes, num_neighbors)
         return sampling.LazyNeighborList(batch, "ids"), sampling.LazyNeighborList(batch, "weights")
 
-    # ---- PPR helpers: on the reference's class surface (utils/random_walk.py:144-229) but called by nothing
-    # (out of scope for kernels).  Host numpy over the CSR arrays: the reference's in-place
-    # ascending-node sweep is reproduced with a sorted frontier of nodes that hold residual mass, so a sweep costs
-    # O(frontier edges) instead of O(V); pushes to a larger id are seen in the same sweep, to a smaller id in the
-    # next one, exactly as the reference's `for node, res in enumerate(residual)` does.
+    # ---- PPR neighbourhoods (reference utils/random_walk.py:144-229; called by nothing upstream, but the reference's second
+    # source of (neighbors, weights) and the only one that needs no RNG).  ppr_method = "device" (default): the level-scheduled
+    # pull sweeps of csrc/ppr_push.hip, every source of the batch at once, bit-identical with the reference's python floats
+    # (pinsage_hip/ppr.py).  ppr_method = "host": numpy over the CSR arrays, one source at a time -- the reference's in-place
+    # ascending-node sweep with a sorted frontier of nodes that hold residual mass; kept as the cross-check.  Both treat a
+    # source beyond the graph as a node without edges (the reference raises IndexError there, :180).
+    ppr_method = "device"
+
+    def ppr_batch(self, nodes, num_neighbors=10, alpha=0.15, num_iterations=10, *, max_target=None):
+        """-> sampling.WeightedBatch on the device: per node its `num_neighbors` best PPR targets and their normalised weights
+        (precompute_top_neighbors without the python dict; `max_target`: only ids below it compete, e.g. the items)."""
+        from pinsage_hip import ppr
+        nodes = nodes.tolist() if isinstance(nodes, torch.Tensor) else list(nodes)
+        return ppr.ppr_topk(self.graph, nodes, int(num_neighbors), alpha, num_iterations, max_target=max_target)
+
+    def _ppr_on_device(self):
+        if self.ppr_method not in ("device", "host"):
+            raise ValueError(f"ppr_method must be 'device' or 'host', not {self.ppr_method!r}")
+        return self.ppr_method == "device"
+
     def _ppr_host_csr(self):
         if getattr(self, "_ppr_csr", None) is None:
             g = self.graph
@@ -158,6 +174,12 @@ class RandomWalkSampler:
 
     def compute_ppr_matrix(self, nodes, alpha=0.15, num_iterations=10):
         nodes = nodes.tolist() if isinstance(nodes, torch.Tensor) else list(nodes)
+        if self._ppr_on_device():
+            from pinsage_hip import ppr
+            scores = ppr.ppr_scores(self.graph, nodes, alpha, num_iterations)
+            at = torch.nonzero(scores > 0)                        # row-major: source order, then ascending target
+            rows, cols, vals = at[:, 0].tolist(), at[:, 1].tolist(), scores[at[:, 0], at[:, 1]].tolist()
+            return {(nodes[i], t): v for i, t, v in zip(rows, cols, vals)}
         size = max(self.graph.V, max(nodes) + 1)
         table = {}
         for s in nodes:
@@ -167,6 +189,9 @@ class RandomWalkSampler:
 
     def precompute_top_neighbors(self, nodes, num_neighbors=10):
         nodes = nodes.tolist() if isinstance(nodes, torch.Tensor) else list(nodes)
+        if self._ppr_on_device() and num_neighbors >= 1:          # a count below 1 is a python slice: the dict path below
+            ids, wts, nvalid = self.ppr_batch(nodes, num_neighbors).host()
+            return {s: (ids[i, :nvalid[i]].tolist(), wts[i, :nvalid[i]].tolist()) for i, s in enumerate(nodes)}
         table = self.compute_ppr_matrix(nodes)
         per_source = {}
         for (s, t), v in table.items():                       # dict order = ascending target per source
