@@ -255,7 +255,8 @@ int ps_gather_max(const float *x, int64_t N, int H, const int32_t *ids, const in
  * PS_EINVAL for M < 2 (the unbiased variance does not exist), N < 1, a null pointer or a short workspace.
  *
  * ps_bn_apply: y[r,c] = epilogue(fmaf(z[r,c] - mean[c], scale[c], beta[c])), one wave per row.  flags: PS_RELU (t < 0 ? +0 : t),
- * PS_L2NORM (the row divided by fmaxf(sqrtf(sum_c t^2), 1e-12f); the sum is a per-lane fmaf chain over the lane's columns in
+ * PS_L2NORM (the row divided by nrm = sqrtf(sum_c t^2), 1e-12f where nrm < 1e-12f -- a NaN norm stays, so a row with a NaN is NaN
+ * throughout, as F.normalize's clamp_min leaves it; the sum is a per-lane fmaf chain over the lane's columns in
  * ascending order, then the wave sum of the other row kernels); any other bit: PS_EINVAL.  y may be z: in place gives the bits of
  * out of place.  PS_OK for M == 0, whatever the pointers; PS_EINVAL for N < 1 or (M > 0) a null pointer.
  * With mean = running_mean and scale = gamma / sqrt(running_var + eps) this is eval-mode batch norm. */

@@ -178,7 +178,10 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float *z, int64_t M
             }
         }
         float nrm = 1.f;
-        if (l2) nrm = fmaxf(sqrtf(ps_wave_sum_f32(acc)), 1e-12f);
+        if (l2) {
+            nrm = sqrtf(ps_wave_sum_f32(acc));
+            nrm = nrm < 1e-12f ? 1e-12f : nrm;                           // a NaN norm stays (fmaxf would drop it): the whole row is NaN
+        }
 #pragma unroll
         for (int k = 0; k < KEEP; ++k) {
             const int col = k * chunk + lane * VEC;

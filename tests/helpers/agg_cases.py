@@ -6,7 +6,12 @@
   max-pool    out_i = max_j relu(W x[n_j] + b), per column; zeros for a row without neighbours
 
 and of the two C entry points over padded (ids, nvalid) with their keep rule (include/pinsage_hip.h).  numpy only: shared by
-tests/test_agg_cases.py (CPU) and tests/test_hip_aggregators.py (GPU)."""
+tests/test_agg_cases.py (CPU) and tests/test_hip_aggregators.py (GPU).
+
+GATE_CASES, further down, are the rows that reach the launcher gates of csrc/neigh_agg.hip which CASES leaves out (agg_facts /
+plants restate the launcher for that proof, never for an expected value), with attention_scores_exact -- the kernel's fp32
+score of every kept slot, bit for bit -- and attention_bound, the derived distance of its softmax from the fp64 softmax of those
+scores: tests/test_hip_agg_matrix.py."""
 import functools
 
 import numpy as np
@@ -173,3 +178,206 @@ def at_ref(at, features, neighbors, self_features=None):
 def mp_ref(mp, features, neighbors):
     p = {k: t.detach().cpu().numpy() for k, t in mp.state_dict().items()}
     return maxpool_forward_ref(features, neighbors, p["mlp.0.weight"], p["mlp.0.bias"])
+
+
+# ---- the launcher gates CASES does not reach -----------------------------------------------------------------------------------
+# (B, N, C, T, offset, gate): offset = the float operands start one float past a 16-byte boundary
+GATE_CASES = (
+    (9, 40, 65, 3, 0, "scalar path, second sweep of one column"),
+    (9, 40, 130, 5, 0, "scalar path, three sweeps"),
+    (6, 40, 256, 4, 1, "scalar path from alignment, four sweeps"),
+    (5, 90, 8, 65, 0, "one slot in a second slot block"),
+    (5, 200, 8, 130, 0, "three slot blocks, vector path"),
+    (5, 200, 6, 130, 0, "three slot blocks, scalar path"),
+)
+PLANTED = ("over", "huge", "twin", "neg", "negmin", "late", "one")      # the planted rows, the last seven of every gate case
+UNROLL = 8                                  # csrc/neigh_agg.hip
+ROW_GRID_CAP = 256 * 16                     # row_grid(): workgroups of four waves
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def agg_facts(B, N, C, T, offset=0):
+    """ps_attention_weights' launcher and loop bounds restated (coverage proofs and messages only)"""
+    vec = 4 if C % 4 == 0 and not offset else 1
+    grid = min(_cdiv(B, 4), ROW_GRID_CAP)
+    return dict(vec=vec, sweeps=_cdiv(C, 64 * vec), slot_blocks=_cdiv(T, 64), small=T <= 64, grid=grid, passes=_cdiv(B, 4 * grid))
+
+
+def plants(ids, nvalid, N):
+    """what the rows of (ids, nvalid) plant: nvalid beyond T, negative nvalid, and -- T > 64 -- a row whose first 64 slots are all
+    dropped and which keeps a later one"""
+    ids, nvalid = np.asarray(ids), np.asarray(nvalid, dtype=np.int64)
+    T = ids.shape[1]
+    keep = kept(ids, nvalid, N)
+    late = T > 64 and bool((~keep[:, :64].any(axis=1) & keep[:, 64:].any(axis=1)).any())
+    return dict(over=bool((nvalid > T).any()), negative=bool((nvalid < 0).any()), late=late)
+
+
+# name -> predicate over (agg_facts, plants): the gates tests/test_agg_cases.py shows CASES not to reach and GATE_CASES to reach
+AGG_GATES = {
+    "attention_weights_kernel<1>: c0 != 0 reloads u and w2": lambda f, p: f["vec"] == 1 and f["sweeps"] >= 2,
+    "three or more 64-slot blocks": lambda f, p: f["slot_blocks"] >= 3,
+    "nvalid > T": lambda f, p: p["over"],
+    "nvalid < 0": lambda f, p: p["negative"],
+    "T > 64: the first slot block keeps nothing, a later one does": lambda f, p: p["late"],
+}
+
+
+@functools.lru_cache(maxsize=None)
+def gate_case(gi):
+    """Inputs of GATE_CASES[gi], as case(): x, self-free operands u, v, w2, raw ids / nvalid for the two raw entry points.  The
+    rows are max(B - 7, 2) ordinary ones (row 0 keeps all T slots, the others a random count with one slot dropped) and seven
+    planted ones, `rows[name]` (rows are added where B is too small for them):
+      over, huge, twin   the same ids (one slot dropped for T >= 3) under nvalid = T + 5, 2^31 - 1 and T: equal results
+      neg, negmin        nvalid = -1 and -2^31 over legal ids: nothing is kept
+      late               T > 64: slots 0..63 hold -1, N, 2^31 - 1 and the kept slots come after them (T <= 64: one neighbour)
+      one                every kept slot names the same neighbour (one slot dropped for T >= 3): weights of exactly 1 / n"""
+    B, N, C, T, offset, _ = GATE_CASES[gi]
+    rs = np.random.RandomState(5200 + gi)
+    plain = max(B - len(PLANTED), 2)
+    Bt = plain + len(PLANTED)
+    x = rs.standard_normal((N, C)).astype(np.float32)
+    u = rs.standard_normal((Bt, C)).astype(np.float32)
+    v = rs.standard_normal((N, C)).astype(np.float32)
+    w2 = (rs.uniform(-1.0, 1.0, C) / np.sqrt(C)).astype(np.float32)
+    bad = np.array([-1, N, 2 ** 31 - 1], dtype=np.int64).astype(np.int32)
+    ids = rs.randint(0, N, size=(Bt, T)).astype(np.int32)
+    nvalid = np.full(Bt, T, dtype=np.int32)
+    for i in range(1, plain):
+        nvalid[i] = rs.randint(1, T + 1)
+        ids[i, nvalid[i]:] = bad[np.arange(T - nvalid[i]) % 3]
+        if nvalid[i] >= 2:
+            ids[i, i % nvalid[i]] = bad[i % 3]
+    rows = {name: plain + k for k, name in enumerate(PLANTED)}
+    if T >= 3:
+        ids[rows["over"], T // 2] = bad[2]
+    ids[rows["huge"]] = ids[rows["twin"]] = ids[rows["over"]]
+    u[rows["huge"]] = u[rows["twin"]] = u[rows["over"]]
+    nvalid[rows["over"]], nvalid[rows["huge"]] = T + 5, 2 ** 31 - 1
+    nvalid[rows["neg"]], nvalid[rows["negmin"]] = -1, -(2 ** 31)
+    if T > 64:
+        ids[rows["late"], :64] = bad[np.arange(64) % 3]
+    else:
+        nvalid[rows["late"]] = 1
+    ids[rows["one"]] = rs.randint(0, N)
+    if T >= 3:
+        ids[rows["one"], 1] = -1
+    out = dict(B=Bt, N=N, C=C, T=T, offset=offset, x=x, u=u, v=v, w2=w2, nvalid=nvalid, raw_ids=ids, rows=rows,
+               vec=agg_facts(Bt, N, C, T, offset)["vec"])
+    for a in out.values():
+        if isinstance(a, np.ndarray):
+            a.setflags(write=False)
+    return out
+
+
+def wave_sum(lanes):
+    """ps_wave_sum_f32 of fp32 [..., 64]: a balanced binary tree over the lanes in their order (tests/helpers/bn_cases.py)"""
+    a = np.asarray(lanes, dtype=np.float32)
+    assert a.shape[-1] == 64
+    while a.shape[-1] > 1:
+        a = a[..., 0::2] + a[..., 1::2]
+    return a[..., 0]
+
+
+def attention_scores_exact(u, v, w2, ids, nvalid, vec, sequential=False):
+    """fp32 [B, T]: ps_attention_weights' score of every kept slot, -inf elsewhere, in the kernel's order: lane l chains
+    part = fmaf(w2[c], relu(u[c] + v[c]), part) over its columns k * 64 * vec + l * vec + e (sweep k, element e, ascending) from
+    +0.0, the sum u + v rounded and relu as h < 0 -> +0.0; the 64 lanes are then added by ps_wave_sum_f32's balanced tree.  vec:
+    4 when C % 4 == 0 and u, v, w2 are 16-byte aligned, else 1.  sequential: the near miss that adds the lanes one after the
+    other."""
+    from oracle.pinsage_oracle import _fmaf_vec
+    u, v, w2 = (np.asarray(a, dtype=np.float32) for a in (u, v, w2))
+    ids = np.asarray(ids)
+    C = v.shape[1]
+    chunk = 64 * vec
+    sweeps = _cdiv(C, chunk)
+
+    def pad(a):                                           # a column past C: fmaf(0, relu(0 + 0), part) = part (part is never -0.0)
+        out = np.zeros(a.shape[:-1] + (sweeps * chunk,), dtype=np.float32)
+        out[..., :C] = a
+        return out.reshape(a.shape[:-1] + (sweeps, 64, vec))
+    keep = kept(ids, nvalid, v.shape[0])
+    scores = np.full(keep.shape, -np.inf, dtype=np.float32)
+    wp = pad(w2)
+    for i in range(keep.shape[0]):
+        js = np.nonzero(keep[i])[0]
+        if not js.size:
+            continue
+        h = pad(u[i])[None] + pad(v[ids[i, js]])          # fp32, rounded
+        h = np.where(h < 0, np.float32(0.0), h)
+        part = np.zeros((js.size, 64), dtype=np.float32)
+        for k in range(sweeps):
+            for e in range(vec):
+                part = _fmaf_vec(np.broadcast_to(wp[k, :, e], part.shape), h[:, k, :, e], part)
+        if sequential:
+            s = part[:, 0]
+            for lane in range(1, 64):
+                s = s + part[:, lane]
+            scores[i, js] = s
+        else:
+            scores[i, js] = wave_sum(part)
+    return scores
+
+
+def softmax_of_scores(scores):
+    """fp64 [B, T]: the softmax of fp32 scores over the slots that are not -inf, every operation in fp64; zeros elsewhere"""
+    s = np.asarray(scores, dtype=np.float64)
+    out = np.zeros(s.shape, dtype=np.float64)
+    for i in range(s.shape[0]):
+        js = np.nonzero(np.isfinite(s[i]))[0]
+        if js.size:
+            out[i, js] = _softmax64(s[i, js])
+    return out
+
+
+# expf's error bound E in ulp: the measured maximum, 0.8164 ulp over the 18 043 arguments of GATE_CASES and CASES (in [-17.48, 0];
+# profiles/expf_ulp_attention.txt, tools/expf_ulp.py on an MI355X with the library's compiler flags), rounded up, plus one ulp
+EXPF_ULP = 0.82 + 1.0
+
+
+def expf_arguments(scores):
+    """fp32: the arguments s - max (rounded once, as the kernel subtracts) of the kept slots of a score table"""
+    s = np.asarray(scores, dtype=np.float32)
+    rows = np.isfinite(s).any(axis=1)
+    with np.errstate(invalid="ignore"):
+        d = s[rows] - s[rows].max(axis=1, keepdims=True)
+    return d[np.isfinite(d)].astype(np.float32)
+
+
+def attention_bound(scores, T):
+    """fp64 [B, T]: how far ps_attention_weights' fp32 weight of a kept slot may lie from softmax_of_scores(scores), the fp64
+    softmax of the kernel's own fp32 scores (attention_scores_exact).  With u = 2^-24 and a_j the reference weight of slot j:
+
+      the maximum m is exact; d_j = fl(s_j - m) is rounded once, |d_j - (s_j - m)| <= |s_j - m| u, which multiplies the
+      exponential by at most exp(|s_j - m| u) = 1 + |s_j - m| u to first order;
+      expf returns its value within E ulp, a relative error of at most E 2^-23 = 2 E u (an ulp is at most 2^-23 of the value);
+      so e_j carries delta_j = (|s_j - m| + 2 E) u;
+      the sum of the e_j goes through at most D = ceil(T / 64) - 1 + 6 additions of non-negative terms (a lane's own slots one
+      after the other, then the six steps of the wave sum), each with relative error u and none amplified -- all terms have one
+      sign --, so the sum carries sum_k a_k delta_k + D u;
+      the division is rounded once: u.
+
+      |attn_j - a_j| <= a_j (delta_j + sum_k a_k delta_k + (D + 2) u) + 2^-149
+
+    one u of the (D + 2) for the second-order terms -- the whole factor stays below 2^-12 here, its square below u / 2 -- and
+    2^-149 for a quotient in the subnormal range.  The derivation needs exp(d_j) to be a normal number: scores more than 80
+    apart within a row are refused.
+    E = EXPF_ULP cannot be derived here, and no copy of HIP's math-accuracy table ships with the toolchain: it is measured by
+    tools/expf_ulp.py, which runs one kernel that evaluates expf on exactly the arguments d_j of GATE_CASES and CASES and
+    compares with fp64 exp of the same fp32 arguments on the host (the library function against the reference, not the kernel
+    under test).  Measured maximum 0.8164 ulp (profiles/expf_ulp_attention.txt); E = that, rounded up, plus one ulp = 1.82."""
+    s = np.asarray(scores, dtype=np.float64)
+    u = 2.0 ** -24
+    D = _cdiv(T, 64) - 1 + 6
+    a = softmax_of_scores(scores)
+    fin = np.isfinite(s)
+    with np.errstate(invalid="ignore"):
+        gap = np.where(fin, np.where(fin, s, -np.inf).max(axis=1, keepdims=True) - np.where(fin, s, 0.0), 0.0)
+    assert (gap <= 80.0).all()
+    delta = np.where(fin, (gap + 2.0 * EXPF_ULP) * u, 0.0)
+    factor = delta + (a * delta).sum(axis=1, keepdims=True) + (D + 2) * u
+    assert (factor < 2.0 ** -12).all()
+    return np.where(fin, a * factor + 2.0 ** -149, 0.0)

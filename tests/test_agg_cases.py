@@ -164,3 +164,92 @@ def test_entry_points_check_their_arguments():
     for hd, t in ((0, 2), (-1, 2), (4, 0), (4, -3)):
         assert aw(p, p, 4, hd, p, p, p, 1, t, p, null) == nv.PS_EINVAL and gm(p, 4, hd, p, p, 1, t, p, null) == nv.PS_EINVAL
     assert aw(p, p, 4, 4, p, p, p, -1, 2, p, null) == nv.PS_EINVAL and gm(p, 4, 4, p, p, -1, 2, p, null) == nv.PS_EINVAL
+
+
+# ---- GATE_CASES: the launcher gates of csrc/neigh_agg.hip that CASES leaves out -----------------------------------------------
+GATE_IDS = [f"g{gi}-B{c[0]}-N{c[1]}-C{c[2]}-T{c[3]}" + ("-offset" if c[4] else "") for gi, c in enumerate(ac.GATE_CASES)]
+
+
+def test_gate_table_is_the_issues_and_reaches_what_the_old_table_does_not():
+    assert [c[:5] for c in ac.GATE_CASES] == [(9, 40, 65, 3, 0), (9, 40, 130, 5, 0), (6, 40, 256, 4, 1), (5, 90, 8, 65, 0),
+                                              (5, 200, 8, 130, 0), (5, 200, 6, 130, 0)]
+    assert len({c[:5] for c in ac.GATE_CASES}) == len(ac.GATE_CASES) and all(c[5] for c in ac.GATE_CASES)
+    old = []
+    for ci, (B, N, C, T, _) in enumerate(ac.CASES):
+        c = ac.case(ci)
+        old.append((ac.agg_facts(B, N, C, T, int(ci == ac.OFFSET_CASE)), ac.plants(c["raw_ids"], c["nvalid"], N)))
+    new = {}
+    for gi, g in enumerate(ac.GATE_CASES):
+        c = ac.gate_case(gi)
+        new[GATE_IDS[gi]] = (ac.agg_facts(c["B"], g[1], g[2], g[3], g[4]), ac.plants(c["raw_ids"], c["nvalid"], g[1]))
+    for gate, reached in ac.AGG_GATES.items():
+        assert not any(reached(f, p) for f, p in old), gate
+        rows = [n for n, (f, p) in new.items() if reached(f, p)]
+        print(f"{gate}: {rows}")
+        assert rows, gate
+    f = [new[n][0] for n in GATE_IDS]
+    assert [(x["vec"], x["sweeps"]) for x in f[:3]] == [(1, 2), (1, 3), (1, 4)] and 65 - 64 == 1
+    assert ac.agg_facts(*ac.GATE_CASES[2][:4])["vec"] == 4                                   # scalar from the alignment alone
+    assert [(x["vec"], x["slot_blocks"]) for x in f[3:]] == [(4, 2), (4, 3), (1, 3)] and 65 - 64 == 1
+    assert all(p["over"] and p["negative"] for _, p in new.values())
+    assert [p["late"] for _, p in new.values()] == [False, False, False, True, True, True]
+    assert max(x["slot_blocks"] for x, _ in old) == 2 and max(x["sweeps"] for x, _ in old if x["vec"] == 1) == 1
+
+
+@pytest.mark.parametrize("gi", range(len(ac.GATE_CASES)), ids=GATE_IDS)
+def test_gate_case_plants_what_it_says(gi):
+    c = ac.gate_case(gi)
+    N, T, r = c["N"], c["T"], c["rows"]
+    ids, nv = c["raw_ids"], c["nvalid"]
+    keep = ac.kept(ids, nv, N)
+    assert c["B"] >= ac.GATE_CASES[gi][0] and sorted(r.values()) == list(range(c["B"] - 7, c["B"]))
+    assert [int(nv[r[k]]) for k in ("over", "huge", "twin", "neg", "negmin")] == [T + 5, 2 ** 31 - 1, T, -1, -2 ** 31]
+    assert np.array_equal(ids[r["over"]], ids[r["twin"]]) and np.array_equal(ids[r["huge"]], ids[r["twin"]])
+    assert np.array_equal(c["u"][r["over"]], c["u"][r["twin"]]) and np.array_equal(c["u"][r["huge"]], c["u"][r["twin"]])
+    assert np.array_equal(keep[r["over"]], keep[r["twin"]]) and np.array_equal(keep[r["huge"]], keep[r["twin"]])
+    assert keep[r["twin"]].sum() == (T - 1 if T >= 3 else T)
+    assert not keep[r["neg"]].any() and not keep[r["negmin"]].any() and ((ids[r["neg"]] >= 0) & (ids[r["neg"]] < N)).all()
+    if T > 64:
+        assert not keep[r["late"], :64].any() and keep[r["late"], 64:].all()
+        assert {-1, N, 2 ** 31 - 1} == set(ids[r["late"], :64].tolist())
+    one = ids[r["one"]][keep[r["one"]]]
+    assert len(set(one.tolist())) == 1 and one.size == (T - 1 if T >= 3 else T)
+    assert keep[0].all() and {-1, N, 2 ** 31 - 1} <= set(ids.ravel().tolist())
+
+
+@pytest.mark.parametrize("gi", range(len(ac.GATE_CASES)), ids=GATE_IDS)
+def test_exact_scores_and_their_softmax(gi):
+    """the softmax of the exact fp32 scores lies inside the tolerance the fp64 reference is held to
+    (tests/test_hip_aggregators.py::test_attention_weights), clamped rows equal their twin, a row whose kept slots all name one
+    neighbour has reference weights of exactly 1 / n, and the derived bound is far below that tolerance"""
+    c = ac.gate_case(gi)
+    r = c["rows"]
+    s = ac.attention_scores_exact(c["u"], c["v"], c["w2"], c["raw_ids"], c["nvalid"], c["vec"])
+    keep = ac.kept(c["raw_ids"], c["nvalid"], c["N"])
+    assert s.dtype == np.float32 and np.array_equal(np.isfinite(s), keep) and np.isneginf(s[~keep]).all()
+    a = ac.softmax_of_scores(s)
+    ref = ac.attention_weights_ref(c["u"], c["v"], c["w2"], c["raw_ids"], c["nvalid"])
+    np.testing.assert_allclose(a, ref, rtol=ac.RTOL, atol=ac.ATOL)
+    assert np.array_equal(s[r["over"]], s[r["twin"]]) and np.array_equal(s[r["huge"]], s[r["twin"]])
+    n = int(keep[r["one"]].sum())
+    assert len(set(s[r["one"]][keep[r["one"]]].tolist())) == 1                                 # equal scores, bit for bit
+    assert (a[r["one"]][keep[r["one"]]] == 1.0 / n).all() and (ref[r["one"]][keep[r["one"]]] == 1.0 / n).all()
+    b = ac.attention_bound(s, c["T"])
+    assert b.shape == a.shape and not b[~keep].any() and (b[keep] > 0).all()
+    assert (b[keep] <= 1e-5 * a[keep] + 2.0 ** -149).all()                                     # at least ten times tighter than RTOL alone
+    print(f"gate {gi}: bound / weight between {np.min(b[keep] / a[keep]):.2e} and {np.max(b[keep] / a[keep]):.2e}")
+
+
+def test_cases_tell_the_scores_from_a_near_miss():
+    """a sequential instead of a tree wave sum; and the other path's lane assignment (vec 4 for 1, 1 for 4)"""
+    seq, lanes = [], []
+    for gi, g in enumerate(ac.GATE_CASES):
+        c = ac.gate_case(gi)
+        args = (c["u"], c["v"], c["w2"], c["raw_ids"], c["nvalid"])
+        s = ac.attention_scores_exact(*args, c["vec"])
+        if not np.array_equal(ac.attention_scores_exact(*args, c["vec"], sequential=True), s):
+            seq.append(GATE_IDS[gi])
+        if g[2] % 4 == 0 and not np.array_equal(ac.attention_scores_exact(*args, 5 - c["vec"]), s):
+            lanes.append(GATE_IDS[gi])
+    print("sequential wave sum differs on", seq, "; the other path's lanes on", lanes)
+    assert seq and lanes
