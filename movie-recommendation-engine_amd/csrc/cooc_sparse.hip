@@ -62,7 +62,6 @@ struct SparseArgs {
 };
 
 inline size_t lds_bytes(int S) { return (size_t)HEADER_BYTES + (size_t)S * 16; }
-inline int64_t round256(int64_t x) { return (x + 255) / 256 * 256; }
 inline int64_t slab_count(int64_t M) {
     const int64_t n = SLAB_BUDGET / (12 * M);
     return n > MAX_SLABS ? MAX_SLABS : n < MIN_SLABS ? MIN_SLABS : n;
@@ -247,7 +246,7 @@ __global__ __launch_bounds__(THREADS) void cooc_sparse_slab_kernel(const SparseA
 
 extern "C" size_t ps_cooc_pairs_sparse_workspace_bytes(int64_t M, int acc_slots) {
     if (M <= 0 || M >= ((int64_t)1 << 31) - 64 || acc_slots < 0 || acc_slots > MAX_SLOTS) return 0;
-    return COUNTERS_BYTES + (size_t)round256(4 * M) + (size_t)(slab_count(M) * 12 * M);
+    return COUNTERS_BYTES + ps_align256((size_t)(4 * M)) + (size_t)(slab_count(M) * 12 * M);
 }
 
 extern "C" int ps_cooc_pairs_sparse(const int64_t *iptr, const int32_t *iuser, const int32_t *imult, const int64_t *eptr,
@@ -285,7 +284,7 @@ extern "C" int ps_cooc_pairs_sparse(const int64_t *iptr, const int32_t *iuser, c
     SparseArgs g{iptr, iuser, imult, eptr, eitem, emult, order, n, U, M, thr, capacity, S, reinterpret_cast<int4 *>(records),
                  reinterpret_cast<unsigned long long *>(count), counters, counters + 1, counters + 2,
                  reinterpret_cast<int32_t *>(ws + COUNTERS_BYTES),
-                 reinterpret_cast<int32_t *>(ws + COUNTERS_BYTES + round256(4 * M))};
+                 reinterpret_cast<int32_t *>(ws + COUNTERS_BYTES + ps_align256((size_t)(4 * M)))};
     hipLaunchKernelGGL(cooc_sparse_kernel, dim3((unsigned)grid), dim3(THREADS), lds, s, g);
     PS_CHECK_LAUNCH();
     hipLaunchKernelGGL(cooc_sparse_slab_kernel, dim3((unsigned)slab_count(M)), dim3(THREADS), 0, s, g);

@@ -16,7 +16,6 @@
 namespace {
 
 constexpr size_t ALIGN = 256;
-inline size_t align_up(size_t x) { return (x + ALIGN - 1) / ALIGN * ALIGN; }
 
 __global__ void prep_keys_kernel(const int64_t *src, int64_t E, uint32_t *keys, uint32_t *vals) {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += (int64_t)gridDim.x * blockDim.x) {
@@ -268,7 +267,7 @@ extern "C" size_t ps_csr_build_workspace_bytes(int64_t E, int64_t V) {
     size_t temp = 0;
     uint32_t *kn = nullptr;
     (void)rocprim::radix_sort_pairs(nullptr, temp, kn, kn, kn, kn, (size_t)E, 0u, (unsigned)radix_bits(V), (hipStream_t)0);
-    return 4 * align_up((size_t)E * sizeof(uint32_t)) + align_up(temp) + ALIGN;
+    return 4 * ps_align256((size_t)E * sizeof(uint32_t)) + ps_align256(temp) + ALIGN;
 }
 
 extern "C" int ps_csr_build(const int64_t *src, const int64_t *dst, const float *w, int64_t E, int64_t V,
@@ -281,9 +280,9 @@ extern "C" int ps_csr_build(const int64_t *src, const int64_t *dst, const float 
         return PS_OK;
     }
     if (!src || !dst || !col || !wsorted || !workspace) return PS_EINVAL;
-    const size_t seg = align_up((size_t)E * sizeof(uint32_t));
+    const size_t seg = ps_align256((size_t)E * sizeof(uint32_t));
     if (workspace_bytes < 4 * seg + ALIGN) return PS_EWORKSPACE;
-    char *base = reinterpret_cast<char *>(align_up(reinterpret_cast<size_t>(workspace)));
+    char *base = ps_ws_base(workspace);
     uint32_t *keys_in = reinterpret_cast<uint32_t *>(base);
     uint32_t *keys_out = reinterpret_cast<uint32_t *>(base + seg);
     uint32_t *vals_in = reinterpret_cast<uint32_t *>(base + 2 * seg);

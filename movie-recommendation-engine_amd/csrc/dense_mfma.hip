@@ -25,7 +25,7 @@
 // pinned with sched_group_barrier).  Two blocks per CU (launch bound): the older wave of a SIMD owns the MFMA pipe and
 // the younger runs in its gaps; MFMA and VALU instructions do not overlap on a SIMD, which is what prices the epilogue
 // (tools/gemm_trace.py).
-#include "ps_common.h"
+#include "ps_select.h"
 #include "pool_row.h"
 #include <type_traits>
 
@@ -346,7 +346,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, f32x16 (&acc)[T
     }
     if constexpr (EPI == 3) {
         // ps_hardest_negative: per row the largest similarity and the smallest column that attains it, as one packed word
-        // (ps_best_pack, csrc/ps_common.h).  A lane folds its TN columns of a row, the 32 lanes of a wave half take the integer
+        // (ps_best_pack, csrc/ps_select.h).  A lane folds its TN columns of a row, the 32 lanes of a wave half take the integer
         // maximum, lane r of each half keeps row r's word and adds it to the row's total with ONE vector 64-bit atomic max per
         // 32-row tile (16 rows per half).  Integer max is associative: any order of the column tiles gives the same word.  No
         // [M, N] slab is written.
@@ -1385,7 +1385,7 @@ GcnWorkspace gcn_workspace(int64_t M, int H) {
     w.slab = 0;
     w.ord = (size_t)ps_cdiv(M, 64) * 64 * (size_t)H * sizeof(float);
     w.flag = w.ord + (size_t)ps_cdiv(M, 64) * 64 * sizeof(int32_t);
-    w.total = w.flag + ((size_t)ps_cdiv(M, 64) * sizeof(int32_t) + 255) / 256 * 256;      // one flag per tile
+    w.total = w.flag + ps_align256((size_t)ps_cdiv(M, 64) * sizeof(int32_t));      // one flag per tile
     return w;
 }
 

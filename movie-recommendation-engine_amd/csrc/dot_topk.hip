@@ -7,11 +7,11 @@
 // row selects the k best: every lane keeps a sorted k-list of its strided elements in an LDS
 // column, and the 64 columns are merged by k wave-wide min-reductions.
 // Order: similarity descending, ties by ascending id (torch.topk leaves tie order unspecified).
-#include "ps_common.h"
+#include "ps_select.h"
 
 namespace {
 
-constexpr uint64_t EMPTY_KEY = 0xFFFFFFFFFFFFFFFFull;
+constexpr uint64_t EMPTY_KEY = PS_EMPTY64;
 
 __global__ void gather_rows_kernel(const float *__restrict__ E, int D, const int64_t *__restrict__ qidx, int64_t nq,
                                    float *__restrict__ Q) {
@@ -19,17 +19,6 @@ __global__ void gather_rows_kernel(const float *__restrict__ E, int D, const int
         const int64_t r = i / D;
         Q[i] = E[qidx[r] * D + (i - r * D)];
     }
-}
-
-__device__ __forceinline__ uint32_t desc_key(float v) {      // smaller key = larger value
-    const uint32_t b = __float_as_uint(v);
-    const uint32_t u = (b & 0x80000000u) ? ~b : (b | 0x80000000u);   // monotone increasing in v
-    return ~u;
-}
-__device__ __forceinline__ float key_value(uint32_t kk) {
-    const uint32_t u = ~kk;
-    const uint32_t b = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    return __uint_as_float(b);
 }
 
 // Exact selection of the kk smallest 64-bit keys (value key << 32 | id: unique) a wave sees, with ONE threshold for the whole
@@ -82,6 +71,37 @@ struct WaveSelect {
     }
 };
 
+// The sweeps around a WaveSelect, for one row and one wave.  A sweep selects at most kcap keys; k > kcap takes further sweeps,
+// each admitting only keys AFTER the last one emitted -- keys are unique (id in the low word), so the sweeps partition the
+// order exactly.  DESC: largest value first (else smallest); `scan(sel)` offers every candidate of the row once, as
+// topk_key<DESC>(value, id).  Slots beyond the candidates are padding: (-inf or FLT_MAX, -1).
+template <bool DESC>
+__device__ __forceinline__ uint64_t topk_key(float v, uint32_t id) {
+    return ((uint64_t)(DESC ? ~ps_float_order(v) : ps_float_order(v)) << 32) | id;
+}
+template <bool DESC, typename Scan>
+__device__ __forceinline__ void topk_sweeps(uint64_t *queue, int lane, int k, int kcap, float *__restrict__ vals,
+                                            int64_t *__restrict__ ids, Scan scan) {
+    WaveSelect sel{queue, lane, 0, 0, EMPTY_KEY, 0, true};
+    bool dry = false;
+    for (int base = 0; base < k; base += kcap) {
+        const int kk = (k - base) < kcap ? (k - base) : kcap;
+        sel.reset(kk);
+        if (!dry) scan(sel);
+        sel.reduce();
+        for (int r = lane; r < kk; r += 64) {
+            const uint64_t best = r < sel.cnt ? sel.q[r] : EMPTY_KEY;
+            const uint32_t kb = (uint32_t)(best >> 32);
+            vals[base + r] = best != EMPTY_KEY ? ps_float_unorder(DESC ? ~kb : kb) : (DESC ? -INFINITY : 3.4028234663852886e38f);
+            ids[base + r] = best != EMPTY_KEY ? (int64_t)(uint32_t)best : -1;
+        }
+        if (sel.cnt < kk) dry = true;                                 // nothing left: the remaining slots are padding
+        else sel.after = sel.q[kk - 1];
+        sel.first = false;
+        ps_wave_lds_sync();
+    }
+}
+
 // MODE 0: largest similarity first (exact inner-product search).  MODE 1: smallest L2 distance first,
 // dist = |q|^2 + |x|^2 - 2 q.x, optionally restricted to the items whose inverted list (assign) is probed.
 template <int MODE>
@@ -98,50 +118,32 @@ __global__ __launch_bounds__(256) void row_topk_kernel(const float *__restrict__
     const float *s = sims + row * N;
     const int64_t self = exclude_self ? qidx[row] : -1;
     const float qnr = (MODE == 1) ? qn[row] : 0.f;
-    // k > kcap: further sweeps over the row, each admitting only keys AFTER the last one emitted -- keys are unique (id in the
-    // low word), so the sweeps partition the order exactly
-    WaveSelect sel{skeys + wv * SELQ, lane, 0, 0, EMPTY_KEY, 0, true};
-    bool dry = false;
-    for (int base = 0; base < k; base += kcap) {
-        const int kk = (k - base) < kcap ? (k - base) : kcap;
-        sel.reset(kk);
-        if (!dry)
-            for (int64_t j0 = 0; j0 < N; j0 += 512) {              // eight elements per lane requested together
-                float sv[8], xv[8];
-                int32_t av[8];
+    topk_sweeps<MODE == 0>(skeys + wv * SELQ, lane, k, kcap, vals + row * k, ids + row * k, [&](WaveSelect &sel) {
+        for (int64_t j0 = 0; j0 < N; j0 += 512) {                  // eight elements per lane requested together
+            float sv[8], xv[8];
+            int32_t av[8];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int64_t j = j0 + lane + 64 * u;
-                    const bool ok = j < N;
-                    sv[u] = ok ? s[j] : 0.f;
-                    xv[u] = (MODE == 1 && ok) ? xn[j] : 0.f;
-                    av[u] = (MODE == 1 && assign && ok) ? assign[j] : 0;
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int64_t j = j0 + lane + 64 * u;
-                    bool ok = j < N;
-                    float v = sv[u];
-                    if (MODE == 1) {
-                        if (assign && ok && !((probe[row * words + (av[u] >> 5)] >> (av[u] & 31)) & 1u)) ok = false;   // list not probed
-                        v = (qnr + xv[u]) - 2.f * v;
-                    }
-                    if (j == self) v = -INFINITY;
-                    sel.offer(ok, ((uint64_t)(MODE == 1 ? ~desc_key(v) : desc_key(v)) << 32) | (uint32_t)j);
-                }
+            for (int u = 0; u < 8; ++u) {
+                const int64_t j = j0 + lane + 64 * u;
+                const bool ok = j < N;
+                sv[u] = ok ? s[j] : 0.f;
+                xv[u] = (MODE == 1 && ok) ? xn[j] : 0.f;
+                av[u] = (MODE == 1 && assign && ok) ? assign[j] : 0;
             }
-        sel.reduce();
-        for (int r = lane; r < kk; r += 64) {
-            const uint64_t best = r < sel.cnt ? sel.q[r] : EMPTY_KEY;
-            const uint32_t kb = (uint32_t)(best >> 32);
-            vals[row * k + base + r] = best != EMPTY_KEY ? key_value(MODE == 1 ? ~kb : kb) : (MODE == 1 ? 3.4028234663852886e38f : -INFINITY);
-            ids[row * k + base + r] = best != EMPTY_KEY ? (int64_t)(uint32_t)best : -1;
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int64_t j = j0 + lane + 64 * u;
+                bool ok = j < N;
+                float v = sv[u];
+                if (MODE == 1) {
+                    if (assign && ok && !((probe[row * words + (av[u] >> 5)] >> (av[u] & 31)) & 1u)) ok = false;   // list not probed
+                    v = (qnr + xv[u]) - 2.f * v;
+                }
+                if (j == self) v = -INFINITY;
+                sel.offer(ok, topk_key<MODE == 0>(v, (uint32_t)j));
+            }
         }
-        if (sel.cnt < kk) dry = true;                                 // nothing left: the remaining slots are padding
-        else sel.after = sel.q[kk - 1];
-        sel.first = false;
-        ps_wave_lds_sync();
-    }
+    });
 }
 
 __global__ void row_sqnorm_kernel(const float *__restrict__ x, int64_t n, int D, float *__restrict__ out) {
@@ -321,12 +323,8 @@ __global__ __launch_bounds__(256) void ivf_row_topk_kernel(const float *__restri
     const int64_t row = (int64_t)blockIdx.x * 4 + wv;
     if (row >= rows) return;
     const float qnr = qn[row];
-    WaveSelect sel{skeys + wv * SELQ, lane, 0, 0, EMPTY_KEY, 0, true};
-    bool dry = false;
-    for (int base = 0; base < k; base += kcap) {
-        const int kk = (k - base) < kcap ? (k - base) : kcap;
-        sel.reset(kk);
-        for (int pb = 0; pb < nprobe && !dry; pb += 64) {                    // 64 segments per round (nprobe is 20 by default)
+    topk_sweeps<false>(skeys + wv * SELQ, lane, k, kcap, vals + row * k, ids + row * k, [&](WaveSelect &sel) {
+        for (int pb = 0; pb < nprobe; pb += 64) {                    // 64 segments per round (nprobe is 20 by default)
             const int np = (nprobe - pb) < 64 ? (nprobe - pb) : 64;
             // lane pi: segment pi of this round
             int64_t so = -1, j0 = 0;
@@ -348,7 +346,7 @@ __global__ __launch_bounds__(256) void ivf_row_topk_kernel(const float *__restri
                 const int ns = __builtin_amdgcn_readlane(n, seg);
                 const int64_t sos = ((int64_t)__builtin_amdgcn_readlane((int)(so >> 32), seg) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)so, seg);
                 const int64_t j0s = ((int64_t)__builtin_amdgcn_readlane((int)(j0 >> 32), seg) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)j0, seg);
-#pragma unroll
+    #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int jj = off + lane + 64 * u;
                     const bool ok = jj < ns;
@@ -359,10 +357,10 @@ __global__ __launch_bounds__(256) void ivf_row_topk_kernel(const float *__restri
                 off += 256;
             };
             auto process = [&](int buf) __attribute__((always_inline)) {
-#pragma unroll
+    #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const float v = (qnr + xv[buf][u]) - 2.f * sv[buf][u];
-                    sel.offer(iv[buf][u] >= 0, ((uint64_t)(~desc_key(v)) << 32) | (uint32_t)iv[buf][u]);
+                    sel.offer(iv[buf][u] >= 0, topk_key<false>(v, (uint32_t)iv[buf][u]));
                 }
             };
             skip_empty();
@@ -382,17 +380,7 @@ __global__ __launch_bounds__(256) void ivf_row_topk_kernel(const float *__restri
                 }
             }
         }
-        sel.reduce();
-        for (int r = lane; r < kk; r += 64) {
-            const uint64_t best = r < sel.cnt ? sel.q[r] : EMPTY_KEY;
-            vals[row * k + base + r] = best != EMPTY_KEY ? key_value(~(uint32_t)(best >> 32)) : 3.4028234663852886e38f;
-            ids[row * k + base + r] = best != EMPTY_KEY ? (int64_t)(uint32_t)best : -1;
-        }
-        if (sel.cnt < kk) dry = true;
-        else sel.after = sel.q[kk - 1];
-        sel.first = false;
-        ps_wave_lds_sync();
-    }
+    });
 }
 
 constexpr int TOPK_SWEEP = 32;     // keys per lane and sweep: 4 waves x 32 x 64 lanes x 8 B = 64 KiB of LDS
@@ -420,9 +408,9 @@ extern "C" int ps_dot_topk(const float *E, int64_t N, int D, const int64_t *qidx
     if (workspace_bytes < ps_dot_topk_workspace_bytes(nq, N, D, k)) return PS_EWORKSPACE;
     hipStream_t st = ps_stream(stream);
     const int64_t c = chunk_rows(nq, N);
-    char *base = reinterpret_cast<char *>((reinterpret_cast<size_t>(workspace) + 255) / 256 * 256);
+    char *base = ps_ws_base(workspace);
     float *sims = reinterpret_cast<float *>(base);
-    float *Q = reinterpret_cast<float *>(base + ((size_t)c * N * sizeof(float) + 255) / 256 * 256);
+    float *Q = reinterpret_cast<float *>(base + ps_align256((size_t)c * N * sizeof(float)));
     const int kcap = k < TOPK_SWEEP ? k : TOPK_SWEEP;
     for (int64_t q0 = 0; q0 < nq; q0 += c) {
         const int64_t rows = (nq - q0) < c ? (nq - q0) : c;
@@ -457,9 +445,9 @@ extern "C" int ps_l2_topk(const float *X, int64_t N, int D, const float *Q, int6
     if (workspace_bytes < ps_l2_topk_workspace_bytes(nq, N, D, k)) return PS_EWORKSPACE;
     hipStream_t st = ps_stream(stream);
     const int64_t c = chunk_rows(nq, N);
-    char *base = reinterpret_cast<char *>((reinterpret_cast<size_t>(workspace) + 255) / 256 * 256);
+    char *base = ps_ws_base(workspace);
     float *sims = reinterpret_cast<float *>(base);
-    float *xn = reinterpret_cast<float *>(base + ((size_t)c * N * sizeof(float) + 255) / 256 * 256);
+    float *xn = reinterpret_cast<float *>(base + ps_align256((size_t)c * N * sizeof(float)));
     float *qn = xn + (N + 63) / 64 * 64;
     int64_t g = ps_cdiv(N, 4);
     if (g > 4096) g = 4096;
@@ -499,7 +487,7 @@ IvfLayout ivf_layout(int64_t nq, int64_t N, int D, int nlist, int nprobe, int64_
     L.chunk = ivf_chunk(nq, nprobe, nlist, max_list);
     L.max_tiles = (L.chunk * nprobe + 63) / 64 + nlist;
     size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    auto take = [&](size_t bytes) { const size_t o = off; off += ps_align256(bytes); return o; };
     L.slab = take((size_t)L.max_tiles * 64 * (size_t)(max_list > 0 ? max_list : 1) * sizeof(float));
     L.qg = take((size_t)L.max_tiles * 64 * D * sizeof(float));
     L.xn = take((size_t)(N + 64) * sizeof(float));
@@ -533,7 +521,7 @@ extern "C" int ps_ivf_topk(const float *X, int64_t N, int D, const int64_t *list
     const IvfLayout L = ivf_layout(nq, N, D, nlist, nprobe, max_list);
     if (workspace_bytes < L.total) return PS_EWORKSPACE;
     hipStream_t st = ps_stream(stream);
-    char *base = reinterpret_cast<char *>((reinterpret_cast<size_t>(workspace) + 255) / 256 * 256);
+    char *base = ps_ws_base(workspace);
     float *slab = reinterpret_cast<float *>(base + L.slab), *Qg = reinterpret_cast<float *>(base + L.qg);
     float *xn = reinterpret_cast<float *>(base + L.xn), *qn = reinterpret_cast<float *>(base + L.qn);
     int64_t *grp = reinterpret_cast<int64_t *>(base + L.grp), *seg = reinterpret_cast<int64_t *>(base + L.seg);

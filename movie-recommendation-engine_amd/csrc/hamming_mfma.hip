@@ -29,8 +29,8 @@
 //             in the same lane and tile is detected exactly and only then are all rows walked.  A column that would overflow is
 //             compacted and the lane's threshold tightened (exact: ids ascend during the sweep).
 //   merge   : every slice leaves one sorted k-list per query (the two lanes of a query merge theirs in LDS);
-//             slice_merge_kernel merges them by (distance, row): 16 lanes per query, k rounds of a DPP row minimum
-//             (slice_merge64_kernel, one wave per query, when few queries over a large table are cut into 17..64 slices).
+//             slice_merge_kernel<16> merges them by (distance, row): 16 lanes per query, k rounds of a DPP row minimum
+//             (slice_merge_kernel<64>, one wave per query, when few queries over a large table are cut into 17..64 slices).
 // Queries arrive as sign planes (ps_hamming_topk_mfma) or as packed codes (ps_hamming_topk_mfma_codes: the pipelined kernels'
 // workgroups expand their own 32 queries in registers, query_frag; for the older kernels the launcher expands into the workspace).
 // Two generations of sweep kernels live here:
@@ -48,7 +48,7 @@
 // ~30 K cycles with the whole workgroup at its barrier, because room for a whole tile (16 rows per lane) was demanded after
 // every tile.  Asking only for the room the next append needs, and compacting by bisection when a column really is full, took the
 // 256-bit collect pass from 153 to ~100 us (random codes: 94; the straight-line pipeline and the leaner keys are the rest of it).
-#include "ps_common.h"
+#include "ps_select.h"
 #include <type_traits>
 
 namespace {
@@ -83,7 +83,7 @@ extern "C" int ps_debug_hm_times(unsigned long long *host) {
     return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(ps_hm_times), sizeof(unsigned long long) * 4 * 4096);
 }
 #endif
-constexpr uint32_t EMPTY_KEY = 0xffffffffu;
+constexpr uint32_t EMPTY_KEY = PS_EMPTY32;
 constexpr int NBUF = 4;                    // ring entries: one being multiplied (from registers), one being read into registers, two in flight
 constexpr int WAVES = 8;
 constexpr int PAD_TILES = 4;               // plane tables are padded to whole ring entries (2 or 4 item tiles of 32 codes)
@@ -976,31 +976,19 @@ __global__ __launch_bounds__(512, 4) void hamming_pipe_kernel(HArgs a) {
     merge_lane_pair(a, cand, lane2, li2, lh2, q2, cnt, slice, t0);
 }
 
-// Final merge of the per-slice lists: 16 lanes per query, lane j = the head of slice j's sorted list; k rounds of
-// "row minimum of the 64-bit keys distance << 32 | table row" (4 DPP exchange steps, no LDS), the winner advances.
-// One wave = 4 queries.  ids = row + id_offset; missing entries (-1, INT32_MAX) like faiss.
-__device__ __forceinline__ uint64_t row_min_u64(uint64_t v) {
-#define PS_STEP(ctrl)                                                                                         \
-    {                                                                                                         \
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, ctrl, 0xf, 0xf, true); \
-        const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), ctrl, 0xf, 0xf, true); \
-        const uint64_t o = ((uint64_t)hi << 32) | lo;                                                         \
-        v = o < v ? o : v;                                                                                    \
-    }
-    PS_STEP(0xB1) PS_STEP(0x4E) PS_STEP(0x141) PS_STEP(0x140)
-#undef PS_STEP
-    return v;
-}
-
+// Final merge of the per-slice lists: LPQ lanes per query, lane j = the head of slice j's sorted list; k rounds of "minimum of
+// the 64-bit keys distance << 32 | table row across the query's lanes" (DPP, no LDS), the winner advances.  LPQ = 16: a row of
+// the wave per query, up to 16 lists; LPQ = 64: one wave per query (few queries over a large table are cut into more slices, so
+// that they still fill the chip).  ids = row + id_offset; missing entries (-1, INT32_MAX) like faiss.
+template <int LPQ>
 __global__ __launch_bounds__(256) void slice_merge_kernel(const int32_t *__restrict__ din, const int32_t *__restrict__ rin,
                                                           int P, int64_t nq, int k, int64_t id_offset,
                                                           int32_t *__restrict__ dout, int64_t *__restrict__ iout) {
-    const int lane = threadIdx.x & 63, sub = lane & 15;
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t q = wave * 4 + (lane >> 4);
+    const int sub = threadIdx.x & (LPQ - 1);
+    const int64_t q = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / LPQ;
     const bool mine = q < nq && sub < P;
     const int64_t base = mine ? ((int64_t)sub * nq + q) * k : 0;
-    constexpr uint64_t NONE = ~0ull;
+    constexpr uint64_t NONE = PS_EMPTY64;
     auto head = [&](int ptr) -> uint64_t {
         if (!mine || ptr >= k) return NONE;
         const int32_t r = rin[base + ptr];
@@ -1009,36 +997,8 @@ __global__ __launch_bounds__(256) void slice_merge_kernel(const int32_t *__restr
     int ptr = 0;
     uint64_t key = head(0);
     for (int r = 0; r < k; ++r) {
-        const uint64_t m = row_min_u64(key);
+        const uint64_t m = ps_lanes_min<LPQ>(key);
         if (sub == 0 && q < nq) {
-            dout[q * k + r] = m == NONE ? 0x7fffffff : (int32_t)(m >> 32);
-            iout[q * k + r] = m == NONE ? -1 : (int64_t)(uint32_t)m + id_offset;
-        }
-        if (key == m && m != NONE) key = head(++ptr);
-    }
-}
-
-// the same merge for up to 64 lists (few queries over a large table are cut into more slices, so that they still fill the
-// chip): one wave per query, lane j = the head of list j, wave minimum by DPP + v_readlane (ps_wave_min_u64)
-__global__ __launch_bounds__(256) void slice_merge64_kernel(const int32_t *__restrict__ din, const int32_t *__restrict__ rin,
-                                                            int P, int64_t nq, int k, int64_t id_offset,
-                                                            int32_t *__restrict__ dout, int64_t *__restrict__ iout) {
-    const int lane = threadIdx.x & 63;
-    const int64_t q = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    if (q >= nq) return;
-    const bool mine = lane < P;
-    const int64_t base = mine ? ((int64_t)lane * nq + q) * k : 0;
-    constexpr uint64_t NONE = ~0ull;
-    auto head = [&](int ptr) -> uint64_t {
-        if (!mine || ptr >= k) return NONE;
-        const int32_t r = rin[base + ptr];
-        return r < 0 ? NONE : ((uint64_t)(uint32_t)din[base + ptr] << 32) | (uint32_t)r;
-    };
-    int ptr = 0;
-    uint64_t key = head(0);
-    for (int r = 0; r < k; ++r) {
-        const uint64_t m = ps_wave_min_u64(key);
-        if (lane == 0) {
             dout[q * k + r] = m == NONE ? 0x7fffffff : (int32_t)(m >> 32);
             iout[q * k + r] = m == NONE ? -1 : (int64_t)(uint32_t)m + id_offset;
         }
@@ -1085,12 +1045,6 @@ __global__ __launch_bounds__(256) void bound_select_kernel(const int32_t *__rest
     }
 }
 
-int key_shift_bits(int nbits) {
-    int dbits = 1;
-    while ((1 << (dbits - 1)) < nbits) ++dbits;
-    return 32 - dbits;
-}
-
 // 16-byte pieces of the plane table of n codes: whole ring entries (the padding tiles are zero-filled)
 int64_t plane_pieces(int64_t n, int KS) { return (((n + 31) / 32 + PAD_TILES - 1) / PAD_TILES * PAD_TILES) * KS * 64; }
 
@@ -1132,7 +1086,7 @@ Plan make_plan(int64_t nq, int64_t N, int cs, int k) {
     p.IT = IT;
     p.db = k > 12 || p.KS <= 2 || env_int("PS_HAMMING_MFMA_DB", 0) != 0;   // (KS <= 2: four tiles per entry do not fit 128 VGPRs)
     p.cap = column_cap(p.db, k);
-    p.shift = key_shift_bits(cs * 8);
+    p.shift = ps_hamming_key_shift(cs * 8);
     p.tiles = (N + 31) >> 5;
     const int64_t nqt = (nq + 31) >> 5;
     p.nqb = (int)((nqt + WAVES - 1) / WAVES);
@@ -1169,7 +1123,7 @@ Plan make_plan(int64_t nq, int64_t N, int cs, int k) {
     if (p.KS == 8 && p.km == 32) p.km = 16;
     p.sample_tiles = st;
     size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    auto take = [&](size_t bytes) { const size_t o = off; off += ps_align256(bytes); return o; };
     p.off_thr = take((size_t)nq * sizeof(int32_t));
     p.off_bl = take((size_t)nq * p.bslices * 2 * p.km * sizeof(int32_t));
     p.off_i = take((size_t)p.slices * nq * k * sizeof(int32_t));
@@ -1293,7 +1247,7 @@ static int hamming_topk_mfma(const void *qplanes, const uint8_t *qcodes, int64_t
     if ((reinterpret_cast<size_t>(qplanes) | reinterpret_cast<size_t>(dbplanes)) % 16 != 0) return PS_EINVAL;
     if (reinterpret_cast<size_t>(qcodes) % 4 != 0) return PS_EINVAL;
     if (!workspace || workspace_bytes < p.total) return PS_EWORKSPACE;
-    char *base = reinterpret_cast<char *>((reinterpret_cast<size_t>(workspace) + 255) / 256 * 256);
+    char *base = ps_ws_base(workspace);
     int32_t *thr0 = reinterpret_cast<int32_t *>(base + p.off_thr);
     int32_t *bl = reinterpret_cast<int32_t *>(base + p.off_bl);
     int32_t *cr = reinterpret_cast<int32_t *>(base + p.off_i);
@@ -1316,10 +1270,10 @@ static int hamming_topk_mfma(const void *qplanes, const uint8_t *qcodes, int64_t
     }
     if (rc != PS_OK) return rc;
     if (p.slices <= 16)
-        hipLaunchKernelGGL(slice_merge_kernel, dim3((unsigned)ps_cdiv(nq, 16)), dim3(256), 0, st, cd, cr, p.slices, nq, k, id_offset,
+        hipLaunchKernelGGL(slice_merge_kernel<16>, dim3((unsigned)ps_cdiv(nq, 16)), dim3(256), 0, st, cd, cr, p.slices, nq, k, id_offset,
                            dist, ids);
     else
-        hipLaunchKernelGGL(slice_merge64_kernel, dim3((unsigned)ps_cdiv(nq, 4)), dim3(256), 0, st, cd, cr, p.slices, nq, k, id_offset,
+        hipLaunchKernelGGL(slice_merge_kernel<64>, dim3((unsigned)ps_cdiv(nq, 4)), dim3(256), 0, st, cd, cr, p.slices, nq, k, id_offset,
                            dist, ids);
     PS_CHECK_LAUNCH();
     return PS_OK;

@@ -6,10 +6,9 @@
 //
 // Slices of the table are swept by different waves (see hamming_scan_kernel) and merged by
 // ps_topk_merge's kernel.
-#include "ps_common.h"
+#include "ps_select.h"
 
 namespace {
-
 
 // One wave = up to QT (<= 64) queries x one slice of the code table.  Lanes own db items: a chunk of G
 // 64-item groups is loaded once (coalesced, G * WORDS registers per lane) and compared with every query of
@@ -28,7 +27,7 @@ __device__ __forceinline__ uint32_t wave_shr1(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x138, 0xf, 0xf, false);
 }
 
-constexpr uint32_t EMPTY_KEY = 0xffffffffu;
+constexpr uint32_t EMPTY_KEY = PS_EMPTY32;
 
 template <int WORDS, int G>
 __global__ __launch_bounds__(256) void hamming_scan_kernel(const uint32_t *__restrict__ q, int64_t nq,
@@ -140,28 +139,44 @@ __global__ __launch_bounds__(256) void hamming_scan_kernel(const uint32_t *__res
     }
 }
 
-// Merge by selection with 16 lanes per query (four queries per wave): the P * k <= 16 KPL candidates of a query sit in
-// registers (candidate c in lane c % 16, register c / 16); round r picks the smallest (distance, id) after the previous
-// winner: a lane-local scan and a row minimum in four DPP steps (quad_perm xor 1, xor 2, row_half_mirror, row_mirror: every
-// lane ends with the minimum of its 16-lane row; no LDS).  203 VALU instructions per query at P = 8, k = 11; r01's rank merge
-// (every candidate counts the candidates before it, broadcast one by one through v_readlane) spent 1 760: 53 us for 10 000 queries.  Lists need not be sorted; ids are distinct across lists.
-struct MergeKey { uint32_t d, hi, lo; };     // (distance, id) as unsigned words; none = all ones
-__device__ __forceinline__ bool key_less(const MergeKey &a, const MergeKey &b) {
-    return a.d < b.d || (a.d == b.d && (a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo)));
+// Merge of the P k-lists of a query (candidate c = entry c % k of list c / k) by selection over (distance, id) as three unsigned
+// words: round r picks the smallest candidate after the previous winner -- every lane its own, then the minimum across the
+// LPQ lanes that serve the query by DPP (no LDS).  Lists need not be sorted; ids are distinct across lists; an id < 0 is padding.
+__device__ __forceinline__ PsKey96 merge_candidate(const int32_t *__restrict__ din, const int64_t *__restrict__ iin, int64_t dstride,
+                                                   int64_t istride, int k, int64_t q, int ci) {
+    const int p = ci / k, t = ci - p * k;
+    const int64_t o = q * k + t;
+    const int32_t d = din[(int64_t)p * dstride + o];
+    const int64_t id = iin[(int64_t)p * istride + o];
+    // padding becomes PS_EMPTY96 by a mask, not a branch: nothing for the distance's load to wait behind, both are in flight together
+    const uint64_t none = (uint64_t)(id >> 63), u = (uint64_t)id | none;
+    return PsKey96{(uint32_t)d | (uint32_t)none, (uint32_t)(u >> 32), (uint32_t)u};
 }
-__device__ __forceinline__ MergeKey row_min_key(MergeKey v) {
-#define PS_STEP(ctrl)                                                                          \
-    {                                                                                          \
-        MergeKey o;                                                                            \
-        o.d = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v.d, ctrl, 0xf, 0xf, true);        \
-        o.hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v.hi, ctrl, 0xf, 0xf, true);      \
-        o.lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v.lo, ctrl, 0xf, 0xf, true);      \
-        if (key_less(o, v)) v = o;                                                             \
+// best = c when c comes after the last winner and before best
+__device__ __forceinline__ void merge_offer(PsKey96 &best, const PsKey96 &c, const PsKey96 &last, bool first) {
+    if ((first || ps_key_less(last, c)) && ps_key_less(c, best)) best = c;
+}
+// the k rounds of one query; lane_best(last, first) = the lane's smallest candidate after `last`; `writer`: the lane that stores
+template <int LPQ, typename LaneBest>
+__device__ __forceinline__ void merge_rounds(int k, bool writer, int32_t *__restrict__ dout, int64_t *__restrict__ iout,
+                                             LaneBest lane_best) {
+    PsKey96 last = PS_EMPTY96;
+    bool first = true;
+    for (int r = 0; r < k; ++r) {
+        const PsKey96 m = ps_lanes_min<LPQ>(lane_best(last, first));
+        const bool found = !ps_key_none(m);
+        if (writer) {
+            dout[r] = found ? (int32_t)m.d : 0x7fffffff;
+            iout[r] = found ? (int64_t)(((uint64_t)m.hi << 32) | m.lo) : -1;
+        }
+        last = m;              // none once the candidates are exhausted: nothing is "after" it
+        first = false;
     }
-    PS_STEP(0xB1) PS_STEP(0x4E) PS_STEP(0x141) PS_STEP(0x140)
-#undef PS_STEP
-    return v;
 }
+
+// 16 lanes per query (four queries per wave): the P * k <= 16 KPL candidates of a query sit in registers (candidate c in lane
+// c % 16, register c / 16).  203 VALU instructions per query at P = 8, k = 11; r01's rank merge (every candidate counts the
+// candidates before it, broadcast one by one through v_readlane) spent 1 760: 53 us for 10 000 queries.
 template <int KPL>
 __global__ __launch_bounds__(256) void topk_select16_kernel(const int32_t *__restrict__ din, const int64_t *__restrict__ iin,
                                                             int64_t dstride, int64_t istride, int P, int64_t nq, int k,
@@ -169,38 +184,21 @@ __global__ __launch_bounds__(256) void topk_select16_kernel(const int32_t *__res
     const int sub = threadIdx.x & 15;
     const int64_t q = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const int n = P * k;
-    constexpr MergeKey NONE = {0xffffffffu, 0xffffffffu, 0xffffffffu};
-    MergeKey c[KPL];
+    PsKey96 c[KPL];
 #pragma unroll
     for (int r = 0; r < KPL; ++r) {
         const int ci = r * 16 + sub;
-        c[r] = NONE;
-        if (q < nq && ci < n) {
-            const int p = ci / k, t = ci - p * k;
-            const int64_t o = q * k + t;
-            const int64_t id = iin[(int64_t)p * istride + o];
-            if (id >= 0) c[r] = MergeKey{(uint32_t)din[(int64_t)p * dstride + o], (uint32_t)((uint64_t)id >> 32), (uint32_t)id};
-        }
+        c[r] = (q < nq && ci < n) ? merge_candidate(din, iin, dstride, istride, k, q, ci) : PS_EMPTY96;
     }
-    MergeKey last = NONE;
-    bool first = true;
-    for (int r = 0; r < k; ++r) {
-        MergeKey best = NONE;
+    merge_rounds<16>(k, sub == 0 && q < nq, dout + q * k, iout + q * k, [&](const PsKey96 &last, bool first) {
+        PsKey96 best = PS_EMPTY96;
 #pragma unroll
-        for (int j = 0; j < KPL; ++j)
-            if ((first || key_less(last, c[j])) && key_less(c[j], best)) best = c[j];
-        const MergeKey m = row_min_key(best);
-        const bool found = !(m.d == NONE.d && m.hi == NONE.hi && m.lo == NONE.lo);
-        if (sub == 0 && q < nq) {
-            dout[q * k + r] = found ? (int32_t)m.d : 0x7fffffff;
-            iout[q * k + r] = found ? (int64_t)(((uint64_t)m.hi << 32) | m.lo) : -1;
-        }
-        last = m;              // none once the candidates are exhausted: nothing is "after" it
-        first = false;
-    }
+        for (int j = 0; j < KPL; ++j) merge_offer(best, c[j], last, first);
+        return best;
+    });
 }
 
-// one wave per query: k rounds of (lane-local min over strided candidates) + wave min-reduce.
+// one wave per query, beyond 256 candidates: every round streams the lane's strided candidates from memory
 __global__ __launch_bounds__(256) void topk_merge_kernel(const int32_t *__restrict__ din, const int64_t *__restrict__ iin,
                                                          int64_t dstride, int64_t istride, int P, int64_t nq, int k,
                                                          int32_t *__restrict__ dout, int64_t *__restrict__ iout) {
@@ -208,36 +206,12 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const int32_t *__restri
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
     const int n = P * k;
-    for (int64_t qi = wave; qi < nq; qi += nw) {
-        int32_t ld = -1;          // last selected (dist, id): strictly increasing selection
-        int64_t li = -1;
-        for (int r = 0; r < k; ++r) {
-            int32_t bd = 0x7fffffff;
-            int64_t bi = 0x7fffffffffffffffll;
-            for (int c = lane; c < n; c += 64) {
-                const int p = c / k, t = c - p * k;
-                const int64_t o = qi * k + t;
-                const int32_t d = din[(int64_t)p * dstride + o];
-                const int64_t id = iin[(int64_t)p * istride + o];
-                if (id < 0) continue;
-                const bool after = (d > ld) || (d == ld && id > li);
-                const bool better = (d < bd) || (d == bd && id < bi);
-                if (after && better) { bd = d; bi = id; }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const int32_t od = __shfl_xor(bd, o, 64);
-                const int64_t oi = __shfl_xor(bi, o, 64);
-                if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
-            }
-            const bool found = bi != 0x7fffffffffffffffll;
-            if (lane == 0) {
-                dout[qi * k + r] = found ? bd : 0x7fffffff;
-                iout[qi * k + r] = found ? bi : -1;
-            }
-            if (found) { ld = bd; li = bi; } else { ld = 0x7fffffff; li = 0x7fffffffffffffffll; }
-        }
-    }
+    for (int64_t qi = wave; qi < nq; qi += nw)
+        merge_rounds<64>(k, lane == 0, dout + qi * k, iout + qi * k, [&](const PsKey96 &last, bool first) {
+            PsKey96 best = PS_EMPTY96;
+            for (int c = lane; c < n; c += 64) merge_offer(best, merge_candidate(din, iin, dstride, istride, k, qi, c), last, first);
+            return best;
+        });
 }
 
 // Queries per wave.  Small tiles need fewer table slices for the same number of waves (every slice pays its
@@ -249,13 +223,6 @@ int pick_tile(int64_t nq, int64_t table_bytes) {
     return table_bytes >= ((int64_t)256 << 20) ? 32 : 4;
 }
 
-// key = distance << shift | slice-local id: distances of cs-byte codes need log2(8 cs) + 1 bits
-int key_shift(int cs) {
-    int dbits = 1;
-    while ((1 << (dbits - 1)) < cs * 8) ++dbits;
-    return 32 - dbits;
-}
-
 int pick_splits(int64_t nq, int64_t N, int cs) {
     const int qt = pick_tile(nq, N * cs);
     const int64_t tiles = (nq + qt - 1) / qt;
@@ -263,7 +230,7 @@ int pick_splits(int64_t nq, int64_t N, int cs) {
     if (s < 1) s = 1;
     if (s > 1024) s = 1024;
     while (s > 1 && N / s < 1024) s >>= 1;           // keep slices worth sweeping
-    const int64_t cap = (int64_t)1 << key_shift(cs);  // a slice's local ids must fit under the distance bits
+    const int64_t cap = (int64_t)1 << ps_hamming_key_shift(cs * 8);  // a slice's local ids must fit under the distance bits
     const int64_t smin = (N + cap - 1) / cap;
     if (s < smin) s = smin;
     return (int)s;
@@ -326,9 +293,8 @@ extern "C" int ps_hamming_topk(const uint8_t *qcodes, int64_t nq, const uint8_t 
     int32_t *cd = dist;
     int64_t *ci = ids;
     if (s > 1) {
-        const size_t need = (size_t)s * nq * k * (sizeof(int32_t) + sizeof(int64_t)) + 512;
-        if (!workspace || workspace_bytes < need) return PS_EWORKSPACE;
-        char *base = reinterpret_cast<char *>((reinterpret_cast<size_t>(workspace) + 255) / 256 * 256);
+        if (!workspace || workspace_bytes < ps_hamming_topk_workspace_bytes(nq, N, cs, k)) return PS_EWORKSPACE;
+        char *base = ps_ws_base(workspace);
         ci = reinterpret_cast<int64_t *>(base);
         cd = reinterpret_cast<int32_t *>(base + (size_t)s * nq * k * sizeof(int64_t));
     }
@@ -338,7 +304,7 @@ extern "C" int ps_hamming_topk(const uint8_t *qcodes, int64_t nq, const uint8_t 
     int kcap = 16;
     while (kcap < k) kcap <<= 1;
     const size_t lds = (size_t)4 * QUERY_TILE * kcap * sizeof(uint32_t);
-    const int shift = key_shift(cs);
+    const int shift = ps_hamming_key_shift(cs * 8);
     const uint32_t *q32 = reinterpret_cast<const uint32_t *>(qcodes);
     const uint32_t *c32 = reinterpret_cast<const uint32_t *>(codes);
 #define PS_LAUNCH_SCAN(WORDS_)                                                                                  \

@@ -1,7 +1,7 @@
 // loss.hip -- the ranking losses of the reference's model/loss.py (MaxMarginRankingLoss, BatchHardTripletLoss, CurriculumLoss)
 // from ONE packed word per query row: the largest negative similarity and the smallest index that attains it.
 //
-//   ps_hardest_negative : best[b] = max_j ps_best_pack(Q_b . X_j, j) (csrc/ps_common.h).  Shared candidates X [N, D]: ps_linear's
+//   ps_hardest_negative : best[b] = max_j ps_best_pack(Q_b . X_j, j) (csrc/ps_select.h).  Shared candidates X [N, D]: ps_linear's
 //                         fp32-MFMA tiles with a row-arg-max epilogue (csrc/dense_mfma.hip, EPI 3), no [B, N] slab.  Per-query
 //                         candidates X [B, N, D]: one thread per candidate row, the fmaf chain of ps_row_dot.  Both are the chain
 //                         acc = fmaf(q[k], x[k], acc), k ascending from +0.0, so the two forms agree bit for bit on equal data.
@@ -9,7 +9,7 @@
 //                         a reduction of fixed shape (per-thread strided sums, then a tree in LDS): the same bits on every run.
 //   ps_margin_loss_bwd  : the closed-form gradient over those indices (include/pinsage_hip.h); every sum over rows runs in
 //                         ascending row order inside one wave -- no float atomics anywhere in this file.
-#include "ps_common.h"
+#include "ps_select.h"
 
 namespace {
 

@@ -666,8 +666,6 @@ __global__ void mt_final_state_kernel(const uint32_t *raw, int64_t w_lo, int64_t
     if (threadIdx.x == 0) pos_out[0] = pos;
 }
 
-inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-
 struct Plan {
     int64_t wa, wb;          // needed output words [wa, wb)
     int64_t key_w;           // stream index of the final key's first word (may be < 0: key unchanged)
@@ -731,9 +729,9 @@ extern "C" size_t ps_mt19937_workspace_bytes(int64_t skip, int64_t n) {
     const Plan p = make_plan(MT_N, skip, n);            // pos only shifts the plan by < 624 words
     int64_t K = p.c1 - p.c0 + 3;
     if (K < 128) K = 128;                               // room for the one-round products of short (ranged) requests
-    const size_t states = align256((size_t)(K + 4) * JP * MT_N * 4);
-    const size_t seqs = align256((size_t)(K / 2 + 2) * SEQ_PAD * 4);
-    return states + seqs + align256((size_t)(p.w_hi - p.w_lo + 2 * MT_N + CHUNK) * 4) + 4096;
+    const size_t states = ps_align256((size_t)(K + 4) * JP * MT_N * 4);
+    const size_t seqs = ps_align256((size_t)(K / 2 + 2) * SEQ_PAD * 4);
+    return states + seqs + ps_align256((size_t)(p.w_hi - p.w_lo + 2 * MT_N + CHUNK) * 4) + 4096;
 }
 
 static int mt_generate(const uint32_t *state_in, int pos_in, int64_t skip, int64_t n, double *out, uint32_t *raw_out,
@@ -768,15 +766,15 @@ static int mt_generate(const uint32_t *state_in, int pos_in, int64_t skip, int64
     const int64_t K = p.c1 - p.c0 + 1;
     if (workspace_bytes < ps_mt19937_workspace_bytes(skip, n)) return PS_EWORKSPACE;
     if ((p.c1 >> (jump_levels - CHUNK_LOG2)) != 0) return PS_EUNSUPPORTED;   // offset beyond the polynomial table
-    char *base = reinterpret_cast<char *>(align256(reinterpret_cast<size_t>(workspace)));
+    char *base = ps_ws_base(workspace);
     const size_t WSZ = (size_t)JP * MT_N;                                    // words per stored window
     uint32_t *states = reinterpret_cast<uint32_t *>(base);                   // [K] chunk windows (JP parts each)
     const int64_t Kc = K > 126 ? K : 126;                                    // the regions are carved for at least 126 windows (workspace_bytes: 128)
     uint32_t *tmpA = states + (size_t)(Kc + 1) * WSZ;                        // ping-pong for the base jump
     uint32_t *tmpB = tmpA + WSZ;
     uint32_t *word0 = tmpB + WSZ;
-    uint32_t *seqs = reinterpret_cast<uint32_t *>(base + align256((size_t)(Kc + 4) * JP * MT_N * 4));
-    uint32_t *raw = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(seqs) + align256((size_t)(Kc / 2 + 2) * SEQ_PAD * 4));
+    uint32_t *seqs = reinterpret_cast<uint32_t *>(base + ps_align256((size_t)(Kc + 4) * JP * MT_N * 4));
+    uint32_t *raw = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(seqs) + ps_align256((size_t)(Kc / 2 + 2) * SEQ_PAD * 4));
     if (raw_out) {                                       // raw mode: the chunk generators write straight into the caller's buffer
         if (p.w_lo != 0) return PS_EUNSUPPORTED;         // (skip = 0: word 2i is the first word of uniform i)
         raw = raw_out;
@@ -854,11 +852,11 @@ static int mt_generate(const uint32_t *state_in, int pos_in, int64_t skip, int64
     }
     if (one_round) {
         char *q = reinterpret_cast<char *>(seqs);
-        const char *q_end = q + align256((size_t)(Kc / 2 + 2) * SEQ_PAD * 4);
-        seqM = reinterpret_cast<uint32_t *>(q);       q += align256((size_t)SEQ_PAD * 4);
-        planes1 = reinterpret_cast<uint32_t *>(q);    q += align256((size_t)32 * PLW * 4);
-        polyAw = reinterpret_cast<uint4 *>(q);        q += align256((size_t)ngroups * KS_TOTAL * 64 * 16);
-        plainS = reinterpret_cast<uint32_t *>(q);     q += align256((size_t)Kw * MT_N * 4);
+        const char *q_end = q + ps_align256((size_t)(Kc / 2 + 2) * SEQ_PAD * 4);
+        seqM = reinterpret_cast<uint32_t *>(q);       q += ps_align256((size_t)SEQ_PAD * 4);
+        planes1 = reinterpret_cast<uint32_t *>(q);    q += ps_align256((size_t)32 * PLW * 4);
+        polyAw = reinterpret_cast<uint4 *>(q);        q += ps_align256((size_t)ngroups * KS_TOTAL * 64 * 16);
+        plainS = reinterpret_cast<uint32_t *>(q);     q += ps_align256((size_t)Kw * MT_N * 4);
         one_round = q <= q_end && (size_t)parts_w * ngroups * 32 * JT * 32 <= (size_t)(Kc - 1) * WSZ;
         if (!one_round && ranged) return PS_EWORKSPACE;  // (cannot happen with ps_mt19937_workspace_bytes: 126 windows' room at least)
     }
@@ -917,12 +915,12 @@ static int mt_generate(const uint32_t *state_in, int pos_in, int64_t skip, int64
         // product of round B shares its source with 30 others, which is what fills the 32 rows of the MFMA
         const int JA = (int)((K - 1) / 32), nsrcB = JA + 1;
         char *q = reinterpret_cast<char *>(seqs);
-        const char *q_end = q + align256((size_t)(K / 2 + 2) * SEQ_PAD * 4);
-        uint32_t *seqM = reinterpret_cast<uint32_t *>(q);      q += align256((size_t)nsrcB * SEQ_PAD * 4);
-        uint32_t *planes = reinterpret_cast<uint32_t *>(q);    q += align256((size_t)nsrcB * 32 * PLW * 4);
-        uint4 *polyA0 = reinterpret_cast<uint4 *>(q);          q += align256((size_t)KS_TOTAL * 64 * 16);
-        uint4 *polyA1 = reinterpret_cast<uint4 *>(q);          q += align256((size_t)KS_TOTAL * 64 * 16);
-        plainS = reinterpret_cast<uint32_t *>(q);              q += align256((size_t)K * MT_N * 4);
+        const char *q_end = q + ps_align256((size_t)(K / 2 + 2) * SEQ_PAD * 4);
+        uint32_t *seqM = reinterpret_cast<uint32_t *>(q);      q += ps_align256((size_t)nsrcB * SEQ_PAD * 4);
+        uint32_t *planes = reinterpret_cast<uint32_t *>(q);    q += ps_align256((size_t)nsrcB * 32 * PLW * 4);
+        uint4 *polyA0 = reinterpret_cast<uint4 *>(q);          q += ps_align256((size_t)KS_TOTAL * 64 * 16);
+        uint4 *polyA1 = reinterpret_cast<uint4 *>(q);          q += ps_align256((size_t)KS_TOTAL * 64 * 16);
+        plainS = reinterpret_cast<uint32_t *>(q);              q += ps_align256((size_t)K * MT_N * 4);
         // parity planes of every polynomial slice: in the JP-part window store, unused (but for window 0) in this mode
         constexpr int PARTS_A = 32, PARTS_B = 8;
         uint16_t *PLp = reinterpret_cast<uint16_t *>(states + WSZ);

@@ -20,7 +20,6 @@
 namespace {
 
 constexpr size_t ALIGN = 256;
-inline size_t align_up(size_t x) { return (x + ALIGN - 1) / ALIGN * ALIGN; }
 
 // share[e] = w[e] / sum(row), python's sum(): left to right from 0 (utils/random_walk.py:184).  One lane per row: once per graph.
 __global__ void shares_kernel(const int64_t *rowptr, const double *w, int64_t V, double *share) {
@@ -189,7 +188,7 @@ extern "C" int ps_ppr_shares(const int64_t *rowptr, const double *wsorted, int64
 extern "C" size_t ps_ppr_push_workspace_bytes(int64_t Vp, int64_t S) {
     if (Vp <= 0 || S <= 0) return 0;
     const int64_t Sc = chunk_columns(S);
-    return 2 * align_up((size_t)Vp * Sc * sizeof(double)) + 2 * align_up((size_t)Vp * (Sc / 64)) + ALIGN;
+    return 2 * ps_align256((size_t)Vp * Sc * sizeof(double)) + 2 * ps_align256((size_t)Vp * (Sc / 64)) + ALIGN;
 }
 
 extern "C" int ps_ppr_push(const int64_t *in_rowptr, const int32_t *in_src, const double *in_share, int64_t V, int64_t Vp,
@@ -211,8 +210,8 @@ extern "C" int ps_ppr_push(const int64_t *in_rowptr, const int32_t *in_src, cons
     // a launch covers at most all Vp nodes, four (node, slab) waves per workgroup: refused here, before anything is enqueued
     if (ps_cdiv(Vp * nslab, 4) >= ((int64_t)1 << 31)) return PS_EINVAL;
     hipStream_t st = ps_stream(stream);
-    const size_t cbytes = align_up((size_t)Vp * Sc * sizeof(double)), abytes = align_up((size_t)Vp * nslab);
-    char *base = reinterpret_cast<char *>(align_up(reinterpret_cast<size_t>(workspace)));
+    const size_t cbytes = ps_align256((size_t)Vp * Sc * sizeof(double)), abytes = ps_align256((size_t)Vp * nslab);
+    char *base = ps_ws_base(workspace);
     double *c[2] = {reinterpret_cast<double *>(base), reinterpret_cast<double *>(base + cbytes)};
     uint8_t *act[2] = {reinterpret_cast<uint8_t *>(base + 2 * cbytes), reinterpret_cast<uint8_t *>(base + 2 * cbytes + abytes)};
     if (hipMemsetAsync(base, 0, 2 * cbytes + 2 * abytes, st) != hipSuccess) return PS_ELAUNCH;

@@ -35,6 +35,9 @@ bool ps_allow_lds(K kernel, size_t bytes) {
 }
 
 static inline int64_t ps_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// workspaces are carved in 256-byte units from the first 256-byte boundary at or after the caller's pointer
+static inline size_t ps_align256(size_t x) { return (x + 255) / 256 * 256; }
+static inline char *ps_ws_base(void *workspace) { return reinterpret_cast<char *>(ps_align256(reinterpret_cast<size_t>(workspace))); }
 
 // internal (not part of the C ABI): grouped x W^T of csrc/dense_mfma.hip, used by the inverted-file scan
 int psi_linear_grouped(const float *x, int64_t M, int K, const float *W, int ldw, float *y, const int64_t *grp, int max_cols,
@@ -61,24 +64,6 @@ __device__ __forceinline__ double ps_div_rn(double a, double b) {
     const double q1 = nextafter(q, ((r > 0.0) == (b > 0.0)) ? INFINITY : -INFINITY);
     return fabs(fma(-q1, b, a)) < fabs(r) ? q1 : q;
 }
-
-// (similarity, candidate index) as ONE unsigned word whose integer order is "larger similarity first, then smaller index":
-// high half = the float's place in its total order (-inf < ... < -0 < +0 < ... < +inf, every NaN above +inf: a NaN candidate
-// is its row's maximum, as in torch.max), low half = ~index.  Every word of a real candidate is > 0, so 0 = "no candidate",
-// and partial maxima combine with a 64-bit integer max -- in registers or with a vector atomic -- in any order.
-__device__ __forceinline__ unsigned long long ps_best_pack(float v, uint32_t j) {
-    const int32_t b = __float_as_int(v);
-    const uint32_t key = v != v ? 0xffffffffu : (uint32_t)(b ^ ((b >> 31) & 0x7fffffff)) ^ 0x80000000u;
-    return ((unsigned long long)key << 32) | (uint32_t)~j;
-}
-__device__ __forceinline__ float ps_best_sim(unsigned long long w) {       // 0 (no candidate) -> -inf
-    const uint32_t key = (uint32_t)(w >> 32);
-    if (w == 0ull) return __int_as_float((int)0xff800000u);
-    if (key == 0xffffffffu) return __int_as_float(0x7fc00000);
-    const int32_t k = (int32_t)(key ^ 0x80000000u);
-    return __int_as_float(k ^ ((k >> 31) & 0x7fffffff));
-}
-__device__ __forceinline__ int64_t ps_best_idx(unsigned long long w) { return w == 0ull ? -1 : (int64_t)(uint32_t)~(uint32_t)w; }
 
 // All LDS traffic of a wave is issued in order; this makes earlier LDS writes/atomics of the
 // wave visible to all of its lanes (waits lgkmcnt) and stops the compiler reordering across it.
@@ -111,19 +96,3 @@ __device__ __forceinline__ float ps_wave_sum_f32(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 #undef PS_DPP_MOV
-// Wave-wide minimum of 64-bit keys, result in every lane: the same six DPP steps on both halves of the key (a lane that a step
-// does not reach reads all ones and so keeps its own value), then lane 63
-__device__ __forceinline__ uint64_t ps_wave_min_u64(uint64_t v) {
-#define PS_STEP(ctrl, rows)                                                                                     \
-    {                                                                                                           \
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)(uint32_t)v, ctrl, rows, 0xf, false); \
-        const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)(uint32_t)(v >> 32), ctrl, rows, 0xf, false); \
-        const uint64_t o = ((uint64_t)hi << 32) | lo;                                                           \
-        v = o < v ? o : v;                                                                                      \
-    }
-    PS_STEP(0xB1, 0xf) PS_STEP(0x4E, 0xf) PS_STEP(0x141, 0xf) PS_STEP(0x140, 0xf) PS_STEP(0x142, 0xa) PS_STEP(0x143, 0xc)
-#undef PS_STEP
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, 63);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), 63);
-    return ((uint64_t)hi << 32) | lo;
-}

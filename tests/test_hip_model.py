@@ -556,6 +556,57 @@ def test_topk_merge_vs_lexsort(P, k):
         assert np.array_equal(dm[q], ed) and np.array_equal(im[q], ei), q
 
 
+def _wide_ids_case(P, k, nq=37):
+    """candidate lists whose ids need all 64 bits: (d [P, nq, k] int32, ids [P, nq, k] int64, expected dist, expected ids)"""
+    rs = np.random.RandomState(7000 + P)
+    n = P * k
+    d = rs.choice(np.array([0, 1, 0x7ffffffe], np.int32), size=(P, nq, k))        # long ties; the largest legal distance
+    hi = rs.choice(np.array([0, 1, 2, 1 << 30], np.int64), size=(nq, n))
+    # distinct low words per query, both halves of the unsigned range; a candidate with a larger high word tends to get a
+    # smaller low word, so ascending low word is not ascending id
+    lo = np.stack([np.sort(rs.choice(np.unique(rs.randint(0, 1 << 32, size=4 * n, dtype=np.int64)), size=n, replace=False))[::-1]
+                   [np.argsort(np.argsort(h + rs.rand(n)))] for h in hi])
+    ids = ((hi << 32) | lo).reshape(nq, P, k).transpose(1, 0, 2).copy()
+    short = rs.rand(P, nq, k) < 0.15
+    ids[short] = -1
+    d[short] = 0x7fffffff
+    ids[:, 0] = -1; d[:, 0] = 0x7fffffff                                  # a query without any candidate
+    ed = np.full((nq, k), 0x7fffffff, np.int32); ei = np.full((nq, k), -1, np.int64)
+    bites = 0
+    for q in range(nq):
+        dd, ii = d[:, q].reshape(-1), ids[:, q].reshape(-1)
+        ok = ii >= 0
+        order = np.lexsort((ii[ok], dd[ok]))[:k]
+        ed[q, :order.size] = dd[ok][order]; ei[q, :order.size] = ii[ok][order]
+        by_lo = np.lexsort((ii[ok] & 0xffffffff, dd[ok]))[:k]            # what a merge that ignored the high id word would do
+        bites += not np.array_equal(ii[ok][by_lo], ii[ok][order])
+    assert bites > 0, "the case does not exercise the high id word"
+    return d, ids, ed, ei
+
+
+@pytest.mark.parametrize("P,k", [(2, 11), (5, 11), (8, 11), (20, 11), (30, 11)])
+def test_topk_merge_wide_ids(P, k):
+    """ps_topk_merge with ids (hi << 32) | lo, hi in {0, 1, 2, 2^30}, where among the candidates that tie on distance the order
+    of the low words is not the order of the ids, and distances {0, 1, INT32_MAX - 1} next to the padding value: the high id
+    word decides comparisons in all four 16-lane forms (P k <= 32 / 64 / 128 / 256) and in the wave-per-query form; 37 queries
+    leave the last wave of either layout ragged.  Oracle: numpy lexsort on (distance, id).  One shape also goes through
+    ps_topk_merge_strided with list strides beyond nq k (candidate records)."""
+    from pinsage_hip import dense
+    d, ids, ed, ei = _wide_ids_case(P, k)
+    nq = d.shape[1]
+    dm, im = dense.topk_merge(torch.from_numpy(d).cuda(), torch.from_numpy(ids).cuda())
+    assert np.array_equal(dm.cpu().numpy(), ed) and np.array_equal(im.cpu().numpy(), ei)
+    if P == 8:
+        n = nq * k
+        rec = (12 * n + 24 + 7) // 8 * 8
+        records = np.full((P, rec), 0xa5, np.uint8)
+        records[:, :8 * n] = ids.reshape(P, n).view(np.uint8)
+        records[:, 8 * n:12 * n] = d.reshape(P, n).view(np.uint8)
+        assert rec // 4 > n and rec // 8 > n
+        dr, ir = dense.topk_merge_records(torch.from_numpy(records).cuda(), nq, k)
+        assert np.array_equal(dr.cpu().numpy(), ed) and np.array_equal(ir.cpu().numpy(), ei)
+
+
 # ---- ADVICE r1 (medium) regressions ----------------------------------------------------------------------------
 def test_graphconv_rejects_out_of_range_edge_index():
     """global ids with batch-local features must raise like torch / PyG do, not corrupt device memory"""
