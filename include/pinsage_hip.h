@@ -237,6 +237,73 @@ int ps_attention_weights(const float *u, const float *v, int64_t N, int Hd, cons
 int ps_gather_max(const float *x, int64_t N, int H, const int32_t *ids, const int32_t *nvalid, int64_t B, int T, float *out,
                   ps_stream_t stream);
 
+/* ---- a9, backward: the gradients of the three neighbour gathers above (ps_importance_pool, ps_attention_weights followed by
+ * ps_importance_pool, ps_gather_max), csrc/neigh_agg_bwd.hip.  The backward of a gather is a scatter; it is computed as a gather
+ * over the TRANSPOSED index, so no float is added atomically and every output bit is a function of the inputs.  Caller-allocated
+ * buffers, no allocation, no synchronisation; PS_OK for an empty problem (B == 0, or N == 0 where N is the row count of the
+ * output), whatever the pointers; PS_EINVAL for a non-positive width / T, a null pointer on a non-empty problem or a short
+ * workspace.  Workspaces are not preserved between calls and need no alignment.
+ *
+ * Slot lists.  A slot is s = i * T + j (B * T < 2^31, else PS_EINVAL).  rptr int64[N + 1] / slots int32[nnz] list, per feature row
+ * r, the KEPT slots whose id is r: S(r) = slots[rptr[r] .. rptr[r + 1]), ascending; rptr[0] = 0, rptr non-decreasing,
+ * rptr[N] = nnz <= B * T (pinsage_hip/sampling.py: slot_lists).  Offsets are clamped to [0, B * T] on the device and a slot outside
+ * [0, B * T) contributes nothing, so no access leaves g / coef / arg; the caller guarantees that slots holds rptr[N] entries.
+ * Segments: S(r) is cut into consecutive segments of SEG = ps_gather_bwd_segment() slots (a compile-time constant); every segment
+ * is its own chain from +0.0 and a row's result is ((p_0 + p_1) + p_2) + ... over its segment results in ascending order (p_0
+ * alone for a row of at most SEG slots).  An empty S(r) gives +0.0 in every column; every element of the output is written.
+ *
+ * ps_pool_weights: w_eff float[B,T] = the weight ps_importance_pool multiplies x[ids[i,j]] by, bit for bit -- the keep rule,
+ *   fp32(count / total), the lane-tree sum and the IEEE division of the a5 / a9 block above -- and +0.0 in every slot that is not
+ *   kept.  lanes selects the tree: 16 = entry e in lane e % 16 of a 16-lane group, what ps_importance_pool uses for T <= 64 with
+ *   H % 4 == 0 and 16-byte aligned x / out (csrc/pool_row.h: pool4_weights, the forward's own code); 64 = lane e % 64 of the wave.
+ *   lanes = 16 with T > 64 means 64, as in the forward; any other value: PS_EINVAL.  max_idx is taken as given (the forward clamps
+ *   it to N - 1: pass the clamped value).  ps_importance_pool(x, wts = w_eff, renorm = 0) repeats the forward's bits.
+ *
+ * ps_gather_bwd: g float[B,H], gx float[N,H]; exactly one of coef float[B*T] and arg int32[B,H] is given (else PS_EINVAL).
+ *   coef: gx[r,c] = the chain acc = fmaf(coef[s], g[s / T, c], acc) over the slots s of a segment, ascending, from +0.0 -- the
+ *         gradient of ps_importance_pool with coef = w_eff, of the attention sum with coef = attn;
+ *   arg : acc = acc + g[i,c] over those slots s = i * T + j of the segment with arg[i,c] == j -- the gradient of ps_gather_max_arg.
+ *   workspace: ps_gather_bwd_workspace_bytes(B, T, H).  B == 0 with N > 0 writes zeros.  Two launches: the segment chains
+ *   (a row of at most SEG slots goes straight to gx), then the sums of the cut rows.
+ *
+ * ps_gather_max_arg: ps_gather_max (same out, bit for bit) with arg int32[B,H]: the lowest kept slot j holding a NaN in column c
+ *   if there is one, otherwise the lowest kept slot whose value equals the maximum; -1 for a row that keeps nothing.
+ *
+ * ps_attention_bwd_rows: the gradient of out[i] = sum_j attn[i,j] x[ids[i,j]], attn = ps_attention_weights(u, v, w2), with respect
+ *   to the scores and to everything that is indexed by the target row.  x float[N,H], g float[B,H] (the gradient of out), attn as
+ *   the forward wrote it; one wave per target row, the keep rule of ps_attention_weights.
+ *     da_ij = sum_c g[i,c] x[id,c]: lane l chains part = fmaf(g[i,c], x[id,c], part) over its columns (c = 64 V k + V l + e, sweep k
+ *             and element e ascending; V = 4 when H % 4 == 0, Hd % 4 == 0 and x, u, v, w2, g, du are 16-byte aligned, else 1) from
+ *             +0.0, columns past H entering as 0 * 0, then the 64 lanes are added by the balanced tree of ps_attention_weights;
+ *     dot_i = the chain fmaf(attn[i,j], da_ij, acc) over the kept j, ascending, from +0.0;
+ *     ds[i,j] = attn[i,j] * (da_ij - dot_i), the difference rounded first; +0.0 in every slot that is not kept (ds float[B,T]);
+ *     du[i,c] = the chain fmaf(ds[i,j], (u[i,c] + v[id,c] > 0 ? w2[c] : 0), acc) over the kept j (du float[B,Hd]);
+ *     share_i[c] = the chain fmaf(ds[i,j], relu(u[i,c] + v[id,c]), acc) with the forward's relu (h < 0 ? +0 : h);
+ *     dw2[c] (float[Hd]) = the sum of the shares in an order that depends on B only: the rows are cut into ceil(B / 128)
+ *             partitions of 128 consecutive rows, a partition is acc = acc + share_i[c] over its rows ascending from +0.0, and
+ *             dw2[c] is acc = acc + partition_p[c] over the partitions ascending from +0.0.
+ *   workspace: ps_attention_bwd_rows_workspace_bytes(B, Hd).  T > 64 works: da is parked in ds between the passes.
+ *   Three launches.  dx of the sum is ps_gather_bwd(coef = attn); the second attention layer's bias drops out of the softmax, so
+ *   its gradient is exactly zero.
+ *
+ * ps_attention_bwd_cols: dv float[N,Hd]: dv[r,c] = the chain fmaf(ds[s], (u[s / T, c] + v[r,c] > 0 ? w2[c] : 0), acc) over S(r), with
+ *   the segment rule and the two launches of ps_gather_bwd; workspace: ps_gather_bwd_workspace_bytes(B, T, Hd). */
+int ps_pool_weights(const int32_t *ids, const int32_t *counts, const float *wts, const int32_t *nvalid, int64_t B, int T,
+                    int64_t max_idx, int renorm, int lanes, float *w_eff, ps_stream_t stream);
+int ps_gather_bwd_segment(void);
+size_t ps_gather_bwd_workspace_bytes(int64_t B, int T, int H);
+int ps_gather_bwd(const int64_t *rptr, const int32_t *slots, int64_t N, int T, const float *coef, const int32_t *arg,
+                  const float *g, int64_t B, int H, float *gx, void *workspace, size_t workspace_bytes, ps_stream_t stream);
+int ps_gather_max_arg(const float *x, int64_t N, int H, const int32_t *ids, const int32_t *nvalid, int64_t B, int T, float *out,
+                      int32_t *arg, ps_stream_t stream);
+size_t ps_attention_bwd_rows_workspace_bytes(int64_t B, int Hd);
+int ps_attention_bwd_rows(const float *x, int64_t N, int H, const float *u, const float *v, int Hd, const float *w2,
+                          const int32_t *ids, const int32_t *nvalid, const float *attn, const float *g, int64_t B, int T, float *ds,
+                          float *du, float *dw2, void *workspace, size_t workspace_bytes, ps_stream_t stream);
+int ps_attention_bwd_cols(const int64_t *rptr, const int32_t *slots, int64_t N, int T, const float *ds, const float *u,
+                          const float *v, int Hd, const float *w2, int64_t B, float *dv, void *workspace, size_t workspace_bytes,
+                          ps_stream_t stream);
+
 /* ---- a9 (model/layers.py): nn.BatchNorm1d of GraphConvLayer.forward with the ReLU and F.normalize behind it (model/layers.py:68-75),
  * csrc/batch_norm.hip.  Caller-allocated buffers, no allocation, no synchronisation, no atomics.
  *

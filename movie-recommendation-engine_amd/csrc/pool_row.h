@@ -41,20 +41,18 @@ __device__ __forceinline__ bool pool_row_keeps(const int32_t *__restrict__ ids, 
     return keep;
 }
 
-// One pooled row per 16-lane group, four rows per wave: the group (lane >> 4) pools row i of ids / counts / wts / nvalid into orow
-// (nothing is read or written when !rok).  All 64 lanes of the wave must call it together (DPP across the group, the entry loop
-// bound is the wave's largest k).  See importance_pool4_kernel for the layout.
+// The final weights of row i in the four-rows-per-wave layout: entry e = p * 16 + l of the row sits in lane l of the row's 16-lane
+// group, page p.  On return id[p] is the entry's id (-1: not kept), w[p] the weight its gathered row is multiplied by (+0.0: not
+// kept) and k = min(nvalid[i], T).  All 64 lanes of the wave must call it together (DPP across the group).  Shared by pool4_row
+// below and by ps_pool_weights (csrc/neigh_agg_bwd.hip), whose backward needs the very weights the forward applied.
 template <int PAGES>
-__device__ __forceinline__ void pool4_row(const float *__restrict__ x, int H, const int32_t *__restrict__ ids,
-                                          const int32_t *__restrict__ counts, const float *__restrict__ wts,
-                                          const int32_t *__restrict__ nvalid, int64_t i, bool rok, int T, int64_t max_idx, int renorm,
-                                          float *__restrict__ orow) {
-    constexpr int TU = 4;                                     // entries gathered per batch
-    const int lane = threadIdx.x & 63, l = lane & 15;
+__device__ __forceinline__ void pool4_weights(const int32_t *__restrict__ ids, const int32_t *__restrict__ counts,
+                                              const float *__restrict__ wts, const int32_t *__restrict__ nvalid, int64_t i, bool rok,
+                                              int T, int64_t max_idx, int renorm, int32_t (&id)[PAGES], float (&w)[PAGES], int &k) {
+    const int l = threadIdx.x & 15;
     // ---- one round trip: nvalid, ids, counts / weights of the wave's four rows ----
-    int k = rok ? nvalid[i] : 0;
-    int32_t id[PAGES], cn[PAGES];
-    float w[PAGES];
+    k = rok ? nvalid[i] : 0;
+    int32_t cn[PAGES];
 #pragma unroll
     for (int p = 0; p < PAGES; ++p) {
         const int e = p * 16 + l;
@@ -83,6 +81,22 @@ __device__ __forceinline__ void pool4_row(const float *__restrict__ x, int H, co
 #pragma unroll
         for (int p = 0; p < PAGES; ++p) w[p] = id[p] >= 0 ? w[p] / wsum : 0.f;
     }
+}
+
+// One pooled row per 16-lane group, four rows per wave: the group (lane >> 4) pools row i of ids / counts / wts / nvalid into orow
+// (nothing is read or written when !rok).  All 64 lanes of the wave must call it together (DPP across the group, the entry loop
+// bound is the wave's largest k).  See importance_pool4_kernel for the layout.
+template <int PAGES>
+__device__ __forceinline__ void pool4_row(const float *__restrict__ x, int H, const int32_t *__restrict__ ids,
+                                          const int32_t *__restrict__ counts, const float *__restrict__ wts,
+                                          const int32_t *__restrict__ nvalid, int64_t i, bool rok, int T, int64_t max_idx, int renorm,
+                                          float *__restrict__ orow) {
+    constexpr int TU = 4;                                     // entries gathered per batch
+    const int lane = threadIdx.x & 63, l = lane & 15;
+    int k;
+    int32_t id[PAGES];
+    float w[PAGES];
+    pool4_weights<PAGES>(ids, counts, wts, nvalid, i, rok, T, max_idx, renorm, id, w, k);
     // entries to walk: the largest k of the four rows (wave-uniform)
     int kmax = __builtin_amdgcn_readlane(k, 0);
     { const int k1 = __builtin_amdgcn_readlane(k, 16), k2 = __builtin_amdgcn_readlane(k, 32), k3 = __builtin_amdgcn_readlane(k, 48);

@@ -4,8 +4,10 @@ signatures.  The gather + weighted reduce of Mean / Weighted / Importance aggreg
 ps_importance_pool (one kernel for the whole batch instead of a python loop per node);
 ImportanceAggregator's Linear runs once on the pooled rows (sum_i w_i (W x_i + b) = W sum_i w_i x_i + b
 because the weights sum to 1), on the fp32-MFMA kernel.  AttentionAggregator and MaxPoolingAggregator run on
-ps_attention_weights + ps_importance_pool and ps_linear + ps_gather_max for CUDA fp32 inputs outside autograd (no
-[B, T, C] tensor is ever built); CPU tensors, other dtypes and training keep the batched torch code (`_forward_torch`).
+ps_attention_weights + ps_importance_pool and ps_linear + ps_gather_max for CUDA fp32 inputs (no [B, T, C] tensor is ever
+built); under autograd the linears are F.linear on the tape and the gather stage is sampling.attention / sampling.max_pool, whose
+backward is the transposed gathers of csrc/neigh_agg_bwd.hip (sampling.grad_method = "torch" restores the torch code there).
+CPU tensors and other dtypes keep the batched torch code (`_forward_torch`).
 """
 from __future__ import annotations
 
@@ -102,6 +104,11 @@ def _cuda_fp32(t):
     return t.is_cuda and t.dtype == torch.float32
 
 
+def _hip_grad(module):
+    """does a call on the autograd tape take the HIP backward?  (sampling.grad_method, fp32 parameters)"""
+    return sampling.grad_method == "hip" and all(p.dtype == torch.float32 for p in module.parameters())
+
+
 class AttentionAggregator(nn.Module):
     """reference model/aggregators.py:93-160.  HIP path: the first attention layer split by columns -- u = self W1[:, :C]^T + b1
     over the B target rows and v = features W1[:, C:]^T over all rows, two ps_linear calls -- then ps_attention_weights
@@ -114,11 +121,24 @@ class AttentionAggregator(nn.Module):
 
     def forward(self, features, neighbors, self_features=None):
         sf = features if self_features is None else self_features
-        if not (_cuda_fp32(features) and _cuda_fp32(sf) and _off_tape(self, features, sf)) or features.dim() != 2 \
+        off_tape = _off_tape(self, features, sf)
+        if not (_cuda_fp32(features) and _cuda_fp32(sf) and (off_tape or _hip_grad(self))) or features.dim() != 2 \
                 or sf.dim() != 2 or sf.size(0) < len(neighbors) or sf.size(1) != features.size(1) \
                 or self.attention[0].in_features != 2 * features.size(1):
             return self._forward_torch(features, neighbors, self_features)       # malformed calls raise what they always raised
-        return self._hip_padded(features, *_pad_dev(neighbors, features), sf)
+        if off_tape:
+            return self._hip_padded(features, *_pad_dev(neighbors, features), sf)
+        return self._hip_tape(features, *_pad_dev(neighbors, features), sf)
+
+    def _hip_tape(self, features, ids, nvalid, self_features):
+        """the HIP path on the autograd tape: the two halves of the first layer are F.linear (torch supplies their gradients),
+        the gather stage is sampling.attention, whose backward is csrc/neigh_agg_bwd.hip"""
+        dev, C, B = features.device, int(features.size(1)), int(ids.size(0))
+        W1, b1 = self.attention[0].weight.to(dev), self.attention[0].bias.to(dev)
+        u = F.linear(self_features[:B], W1[:, :C], b1)
+        v = F.linear(features, W1[:, C:])
+        return sampling.attention(features, u, v, self.attention[2].weight.to(dev).reshape(-1), self.attention[2].bias.to(dev),
+                                  ids, nvalid)
 
     def _hip_padded(self, features, ids, nvalid, self_features):
         """the HIP path over padded device tensors (ids int32 [B,T], nvalid int32 [B])"""
@@ -159,10 +179,20 @@ class MaxPoolingAggregator(nn.Module):
         self.mlp = nn.Sequential(nn.Linear(in_channels, out_channels), nn.ReLU())
 
     def forward(self, features, neighbors):
-        if not (_cuda_fp32(features) and _off_tape(self, features)) or features.dim() != 2 \
+        off_tape = _off_tape(self, features)
+        if not (_cuda_fp32(features) and (off_tape or _hip_grad(self))) or features.dim() != 2 \
                 or features.size(1) != self.mlp[0].in_features:
             return self._forward_torch(features, neighbors)
-        return self._hip_padded(features, *_pad_dev(neighbors, features))
+        if off_tape:
+            return self._hip_padded(features, *_pad_dev(neighbors, features))
+        return self._hip_tape(features, *_pad_dev(neighbors, features))
+
+    def _hip_tape(self, features, ids, nvalid):
+        """the HIP path on the autograd tape: the MLP is F.linear + relu over all rows (torch supplies its gradients), the gather
+        stage is sampling.max_pool, whose backward is csrc/neigh_agg_bwd.hip"""
+        dev = features.device
+        t = F.relu(F.linear(features, self.mlp[0].weight.to(dev), self.mlp[0].bias.to(dev)))
+        return sampling.max_pool(t, ids, nvalid)
 
     def _hip_padded(self, features, ids, nvalid):
         """the HIP path over padded device tensors (ids int32 [B,T], nvalid int32 [B])"""

@@ -186,8 +186,10 @@ class _ListPooling(nn.Module):
         dev = x.device
         ids_t, nvalid_t = torch.from_numpy(ids).to(dev), torch.from_numpy(nvalid).to(dev)
         w_t = torch.from_numpy(w).to(dev) if w is not None else None
-        # sampling.pool keeps its result on the autograd tape when x needs a gradient; ps_gather_max has no backward
-        if _cuda_fp32(x) and x.dim() == 2 and not (self._mode == "max" and torch.is_grad_enabled() and x.requires_grad):
+        # sampling.pool / sampling.max_pool keep their result on the autograd tape when x needs a gradient; with
+        # sampling.grad_method = "torch" the maximum under autograd is the torch code below
+        if _cuda_fp32(x) and x.dim() == 2 and not (self._mode == "max" and torch.is_grad_enabled() and x.requires_grad
+                                                   and sampling.grad_method != "hip"):
             return self._hip_padded(x, ids_t, w_t, nvalid_t)
         return self._torch_padded(x, ids_t, w_t, nvalid_t)
 
@@ -235,7 +237,7 @@ class MaxPoolingLayer(_ListPooling):
         return super()._forward_torch(x, neighbors, None)
 
     def _hip_padded(self, x, ids, w, nvalid):
-        return sampling.gather_max(x, ids, nvalid)
+        return sampling.max_pool(x, ids, nvalid)
 
     def _torch_padded(self, x, ids, w, nvalid):
         mask = torch.arange(ids.shape[1], device=x.device)[None, :] < nvalid[:, None]

@@ -65,6 +65,14 @@ PROTOTYPES = {
     "ps_importance_pool": "i pqippppqiqipp",
     "ps_attention_weights": "i ppqipppqipp",
     "ps_gather_max": "i pqippqipp",
+    "ps_pool_weights": "i ppppqiqiipp",
+    "ps_gather_bwd_segment": "i",
+    "ps_gather_bwd_workspace_bytes": "z qii",
+    "ps_gather_bwd": "i ppqipppqippzp",
+    "ps_gather_max_arg": "i pqippqippp",
+    "ps_attention_bwd_rows_workspace_bytes": "z qi",
+    "ps_attention_bwd_rows": "i pqippipppppqippppzp",
+    "ps_attention_bwd_cols": "i ppqipppipqppzp",
     "ps_bn_stats_workspace_bytes": "z qi",
     "ps_bn_batch_stats": "i pqipffppppppzp",
     "ps_bn_apply": "i pqipppipp",

@@ -475,20 +475,117 @@ def attention_pool(x, u, v, w2, ids, nvalid):
     return importance_pool(x, ids=ids, wts=attn, nvalid=nvalid, renorm=False)
 
 
+# How the backward of the neighbour gathers runs: "hip" = the transposed gathers of csrc/neigh_agg_bwd.hip (no float atomics: the
+# same bits on every run, no [B, T, H] intermediate); "torch" = the torch code that served before (index_add_ for pool, torch
+# autograd of the padded [B, T, C] expressions for max and attention), everywhere.
+grad_method = "hip"
+
+
+def _use_hip_grad(*tensors):
+    if grad_method not in ("hip", "torch"):
+        raise ValueError(f"sampling.grad_method must be 'hip' or 'torch', not {grad_method!r}")
+    return grad_method == "hip" and all(t.is_cuda and t.dtype == torch.float32 for t in tensors)
+
+
+def slot_lists(ids, nvalid, n_rows, max_idx=None):
+    """The transposition of a padded batch: (rptr int64[n_rows + 1], slots int32[B * T]).  slots[rptr[r] : rptr[r + 1]] are the kept
+    slots s = i * T + j (j < min(nvalid[i], T), 0 <= ids[i, j] <= min(max_idx, n_rows - 1)) whose id is r, ascending; the entries
+    of `slots` from rptr[n_rows] on are the slots that are not kept.  A stable sort plus a search per row: plumbing, built once per
+    backward and shared by every transposed gather of it."""
+    B, T = int(ids.size(0)), int(ids.size(1))
+    if B * T >= 2 ** 31:
+        raise ValueError("slot_lists: B * T must stay below 2^31")
+    top = n_rows - 1 if max_idx is None else min(int(max_idx), n_rows - 1)
+    k = nvalid.clamp(min=0, max=T)
+    kept = (torch.arange(T, device=ids.device, dtype=torch.int32)[None, :] < k[:, None]) & (ids >= 0) & (ids <= top)
+    key, order = torch.sort(torch.where(kept, ids, n_rows).reshape(-1), stable=True)
+    # rptr[r] = the first position whose key is >= r (a search per row: no histogram, nothing waits for the host)
+    rptr = torch.searchsorted(key, torch.arange(n_rows + 1, dtype=torch.int32, device=ids.device))
+    return rptr, order.to(torch.int32)
+
+
+def pool_weights(ids, counts=None, wts=None, nvalid=None, max_idx=0, renorm=True, lanes=64):
+    """w_eff[B,T]: the weight ps_importance_pool applies to every slot, bit for bit (+0.0 where a slot is not kept); lanes: the
+    layout of the forward's weight sum (include/pinsage_hip.h)."""
+    B, T = int(ids.size(0)), int(ids.size(1))
+    w_eff = torch.empty((B, T), dtype=torch.float32, device=ids.device)
+    with torch.cuda.device(ids.device):
+        nv.call("ps_pool_weights", nv.ptr(ids), nv.ptr(counts), nv.ptr(wts), nv.ptr(nvalid), B, T, int(max_idx), int(renorm),
+                int(lanes), nv.ptr(w_eff), nv.stream())
+    return w_eff
+
+
+def gather_bwd(rptr, slots, n_rows, T, g, coef=None, arg=None):
+    """gx[n_rows,H]: the transposed gather of g[B,H] over the slot lists -- weighted by coef[B,T], or restricted to the slots
+    arg[B,H] names (ps_gather_bwd)."""
+    B, H = int(g.size(0)), int(g.size(1))
+    gx = torch.empty((n_rows, H), dtype=torch.float32, device=g.device)
+    with torch.cuda.device(g.device):
+        ws, nbytes = nv.workspace("ps_gather_bwd_workspace_bytes", g.device, B, T, H)
+        nv.call("ps_gather_bwd", nv.ptr(rptr), nv.ptr(slots), n_rows, T, nv.ptr(coef), nv.ptr(arg), nv.ptr(g), B, H, nv.ptr(gx),
+                nv.ptr(ws), nbytes, nv.stream())
+    return gx
+
+
+def gather_max_arg(x, ids, nvalid):
+    """(out[B,H], arg int32[B,H]): gather_max and the slot that supplied every maximum (ps_gather_max_arg)"""
+    x, = _rows_fp32("gather_max_arg", x)
+    if ids.dtype != torch.int32 or nvalid.dtype != torch.int32:
+        raise TypeError("ids / nvalid must be int32")
+    B, T = ids.size(0), ids.size(1)
+    N, H = x.size(0), x.size(1)
+    if nvalid.numel() != B:
+        raise ValueError(f"shape mismatch: ids {tuple(ids.shape)}, nvalid {tuple(nvalid.shape)}")
+    out = torch.empty((B, H), dtype=torch.float32, device=x.device)
+    arg = torch.empty((B, H), dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        nv.call("ps_gather_max_arg", nv.ptr(x), N, H, nv.ptr(ids), nv.ptr(nvalid), B, T, nv.ptr(out), nv.ptr(arg), nv.stream())
+    return out, arg
+
+
+def attention_bwd_rows(x, u, v, w2, ids, nvalid, attn, g):
+    """(ds[B,T], du[B,Hd], dw2[Hd]) of ps_attention_bwd_rows"""
+    B, T = int(ids.size(0)), int(ids.size(1))
+    N, H, Hd = int(x.size(0)), int(x.size(1)), int(v.size(1))
+    ds = torch.empty((B, T), dtype=torch.float32, device=x.device)
+    du = torch.empty((B, Hd), dtype=torch.float32, device=x.device)
+    dw2 = (torch.empty if B else torch.zeros)(Hd, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        ws, nbytes = nv.workspace("ps_attention_bwd_rows_workspace_bytes", x.device, B, Hd)
+        nv.call("ps_attention_bwd_rows", nv.ptr(x), N, H, nv.ptr(u), nv.ptr(v), Hd, nv.ptr(w2), nv.ptr(ids), nv.ptr(nvalid),
+                nv.ptr(attn), nv.ptr(g), B, T, nv.ptr(ds), nv.ptr(du), nv.ptr(dw2), nv.ptr(ws), nbytes, nv.stream())
+    return ds, du, dw2
+
+
+def attention_bwd_cols(rptr, slots, T, ds, u, v, w2):
+    """dv[N,Hd] of ps_attention_bwd_cols"""
+    B, N, Hd = int(u.size(0)), int(v.size(0)), int(v.size(1))
+    dv = torch.empty((N, Hd), dtype=torch.float32, device=v.device)
+    with torch.cuda.device(v.device):
+        ws, nbytes = nv.workspace("ps_gather_bwd_workspace_bytes", v.device, B, T, Hd)
+        nv.call("ps_attention_bwd_cols", nv.ptr(rptr), nv.ptr(slots), N, T, nv.ptr(ds), nv.ptr(u), nv.ptr(v), Hd, nv.ptr(w2), B,
+                nv.ptr(dv), nv.ptr(ws), nbytes, nv.stream())
+    return dv
+
+
 class PoolFn(torch.autograd.Function):
-    """Differentiable ps_importance_pool: the forward is the kernel, the backward scatter-adds w_ij * grad_out_i
-    into the feature rows (d out_i / d x_r = sum over the slots j of row i with ids_ij == r of w_ij).  The weights
-    are the ones the kernel used: fp32(count / total) or the given fp32 weights, restricted to the kept slots
-    (j < nvalid, 0 <= id <= max_idx) and, with renorm, divided by their fp32 sum (model/pinsage.py:123-146)."""
+    """Differentiable ps_importance_pool: the forward is the kernel, the backward adds w_ij * grad_out_i into the feature rows
+    (d out_i / d x_r = sum over the slots j of row i with ids_ij == r of w_ij).  The weights are the ones the kernel used:
+    fp32(count / total) or the given fp32 weights, restricted to the kept slots (j < nvalid, 0 <= id <= max_idx) and, with
+    renorm, divided by their fp32 sum (model/pinsage.py:123-146).  grad_method "hip": ps_pool_weights gives those weights bit for
+    bit and ps_gather_bwd sums per feature row over the transposed index; "torch": index_add_ of a [B, T, H] product."""
 
     @staticmethod
     def forward(ctx, x, ids, counts, wts, nvalid, max_idx, renorm):
+        x = x.contiguous()
         out = importance_pool(x, ids=ids, counts=counts, wts=wts, nvalid=nvalid, max_idx=max_idx, renorm=renorm)
         ctx.save_for_backward(ids, counts if counts is not None else wts, nvalid)
         ctx.use_counts = counts is not None
         ctx.n_rows = int(x.size(0))
         ctx.max_idx = ctx.n_rows - 1 if max_idx is None else int(max_idx)
         ctx.renorm = bool(renorm)
+        # the lane layout of the forward's weight sum (ps_importance_pool's own gate)
+        ctx.lanes = 16 if x.size(1) % 4 == 0 and x.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0 else 64
         return out
 
     @staticmethod
@@ -496,6 +593,14 @@ class PoolFn(torch.autograd.Function):
         ids, cw, nvalid = ctx.saved_tensors
         N = ctx.n_rows
         T = ids.size(1)
+        # a backward that is itself recorded (create_graph) keeps the differentiable torch code
+        if _use_hip_grad(grad_out) and ids.numel() < 2 ** 31 and not (torch.is_grad_enabled() and grad_out.requires_grad):
+            g = grad_out.contiguous()                                 # out.sum().backward() hands over a stride-0 tensor
+            top = min(ctx.max_idx, N - 1)
+            w_eff = pool_weights(ids, cw if ctx.use_counts else None, None if ctx.use_counts else cw, nvalid, top, ctx.renorm,
+                                 ctx.lanes)
+            rptr, slots = slot_lists(ids, nvalid, N, top)
+            return gather_bwd(rptr, slots, N, T, g, coef=w_eff), None, None, None, None, None, None
         slot = torch.arange(T, device=ids.device)[None, :]
         inrow = slot < nvalid[:, None]
         kept = inrow & (ids >= 0) & (ids <= ctx.max_idx)
@@ -519,3 +624,108 @@ def pool(x, ids=None, counts=None, wts=None, nvalid=None, max_idx=None, renorm=T
     if torch.is_grad_enabled() and x.requires_grad:
         return PoolFn.apply(x, ids, counts, wts, nvalid, max_idx, renorm)
     return importance_pool(x, ids=ids, counts=counts, wts=wts, nvalid=nvalid, max_idx=max_idx, renorm=renorm)
+
+
+def _kept_mask(ids, nvalid, n_rows):
+    T = ids.size(1)
+    return (torch.arange(T, device=ids.device)[None, :] < nvalid.clamp(min=0, max=T)[:, None]) & (ids >= 0) & (ids < n_rows)
+
+
+def max_pool_torch(x, ids, nvalid):
+    """gather_max as a differentiable torch expression over a padded [B, T, H] tensor (grad_method "torch")"""
+    keep = _kept_mask(ids, nvalid, x.size(0))
+    t = x[torch.where(keep, ids, torch.zeros_like(ids)).long()]
+    t = t.masked_fill(~keep.unsqueeze(2), float("-inf"))
+    out = t.max(dim=1).values if ids.size(1) else t.new_zeros((ids.size(0), x.size(1)))
+    return torch.where(keep.any(dim=1, keepdim=True), out, torch.zeros_like(out))
+
+
+def attention_torch(x, u, v, w2, b2, ids, nvalid):
+    """attention_pool as a differentiable torch expression over padded [B, T, C] tensors (grad_method "torch")"""
+    keep = _kept_mask(ids, nvalid, v.size(0))
+    idt = torch.where(keep, ids, torch.zeros_like(ids)).long()
+    scores = torch.relu(u[:, None, :] + v[idt]) @ w2.reshape(-1) + b2.reshape(())
+    scores = scores.masked_fill(~keep, float("-inf"))
+    has = keep.any(dim=1, keepdim=True)
+    scores = torch.where(has, scores, torch.zeros_like(scores))
+    attn = torch.softmax(scores, dim=1)
+    attn = torch.where(keep, attn, torch.zeros_like(attn))
+    return (x[idt] * attn.unsqueeze(2)).sum(dim=1)
+
+
+class MaxPoolFn(torch.autograd.Function):
+    """Differentiable ps_gather_max: the forward is ps_gather_max_arg, which also records the slot every maximum came from; the
+    backward hands grad_out[i, c] to row ids[i, arg[i, c]] (ps_gather_bwd over the transposed index)."""
+
+    @staticmethod
+    def forward(ctx, x, ids, nvalid):
+        out, arg = gather_max_arg(x, ids, nvalid)
+        ctx.save_for_backward(ids, nvalid, arg)
+        ctx.n_rows = int(x.size(0))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        ids, nvalid, arg = ctx.saved_tensors
+        g = grad_out.contiguous()
+        rptr, slots = slot_lists(ids, nvalid, ctx.n_rows)
+        return gather_bwd(rptr, slots, ctx.n_rows, int(ids.size(1)), g, arg=arg), None, None
+
+
+def max_pool(x, ids, nvalid):
+    """gather_max that stays on the autograd tape when `x` needs a gradient."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        if _use_hip_grad(x) and ids.numel() < 2 ** 31:
+            return MaxPoolFn.apply(x, ids, nvalid)
+        return max_pool_torch(x, ids, nvalid)
+    return gather_max(x, ids, nvalid)
+
+
+class AttentionFn(torch.autograd.Function):
+    """Differentiable attention_pool.  Backward: ps_attention_bwd_rows (ds, du, dw2: one wave per target row), ps_attention_bwd_cols
+    (dv) and ps_gather_bwd with coef = attn (dx), the last two over one shared transposition.  The second layer's bias drops out of
+    the softmax: its gradient is exactly zero."""
+
+    @staticmethod
+    def forward(ctx, x, u, v, w2, b2, ids, nvalid):
+        x, u, v, w2 = _rows_fp32("attention", x, u, v, w2.reshape(-1))
+        if x.size(0) != v.size(0):
+            raise ValueError(f"shape mismatch: x {tuple(x.shape)}, v {tuple(v.shape)}")
+        attn = attention_weights(u, v, w2, ids, nvalid)
+        out = importance_pool(x, ids=ids, wts=attn, nvalid=nvalid, renorm=False)
+        ctx.save_for_backward(x, u, v, w2, ids, nvalid, attn)
+        ctx.b2 = (b2.shape, b2.dtype, b2.device)
+        ctx.w2_shape = w2.shape
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, u, v, w2, ids, nvalid, attn = ctx.saved_tensors
+        need_x, need_u, need_v, need_w2, need_b2 = ctx.needs_input_grad[:5]
+        g = grad_out.contiguous()
+        N, T = int(x.size(0)), int(ids.size(1))
+        dx = du = dv = dw2 = db2 = None
+        if need_x or need_v:
+            rptr, slots = slot_lists(ids, nvalid, N)
+        if need_u or need_v or need_w2:
+            ds, du, dw2 = attention_bwd_rows(x, u, v, w2, ids, nvalid, attn, g)
+            if need_v:
+                dv = attention_bwd_cols(rptr, slots, T, ds, u, v, w2)
+        if need_x:
+            dx = gather_bwd(rptr, slots, N, T, g, coef=attn)
+        if need_b2:
+            db2 = torch.zeros(ctx.b2[0], dtype=ctx.b2[1], device=ctx.b2[2])
+        return dx, du if need_u else None, dv, dw2 if need_w2 else None, db2, None, None
+
+
+def attention(x, u, v, w2, b2, ids, nvalid):
+    """attention_pool that stays on the autograd tape when one of x, u, v, w2, b2 needs a gradient (b2, the second attention
+    layer's bias, receives zeros: it drops out of the softmax)."""
+    floats = (x, u, v, w2, b2)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in floats):
+        if _use_hip_grad(*floats) and ids.numel() < 2 ** 31:
+            return AttentionFn.apply(x, u, v, w2, b2, ids, nvalid)
+        return attention_torch(x, u, v, w2, b2, ids, nvalid)
+    return attention_pool(x, u, v, w2, ids, nvalid)
