@@ -393,11 +393,20 @@ int ps_gcn_layer_ordered(const float *x, int64_t M, int K, const float *W, int l
  *                                  PS_EUNSUPPORTED for such shapes and for A, staged or x not 16-byte aligned.
  *   ps_lsh_stage                 : A float[nbits, D] row-major; staged_bytes below the size: PS_EINVAL.
  * Under the environment switch PS_LSH_STATS=1 a staged ps_lsh_encode adds (dots decided, dots that took the exact chain) to
- * the two uint64 counters at byte 16 of the image -- the one case in which an input is written; off by default. */
+ * the two uint64 counters at byte 16 of the image -- the one case in which an input is written; off by default.
+ *   ps_lsh_encode_planes         : the staged ps_lsh_encode and ps_lsh_expand of its codes (below) in ONE launch: every
+ *                                  workgroup also writes the sign planes of its rows, which it still holds in LDS.  staged:
+ *                                  an image of ps_lsh_stage; planes: ps_lsh_planes_bytes(N, nbits / 8) bytes, all written
+ *                                  (padding tiles included), equal to ps_lsh_expand(codes) bit for bit.  PS_EUNSUPPORTED
+ *                                  where that size is 0 (N = 0, nbits % 64 != 0), where the staged path does not serve the
+ *                                  shape and for x, staged or planes not 16-byte (codes: 4-byte) aligned; a NULL pointer is
+ *                                  PS_EINVAL. */
 #define PS_LSH_STAGED 8
 size_t ps_lsh_stage_bytes(int nbits, int D);
 int ps_lsh_stage(const float *A, int nbits, int D, void *staged, size_t staged_bytes, ps_stream_t stream);
 int ps_lsh_encode(const float *x, int64_t N, int D, const float *A, int nbits, uint8_t *codes, int flags, ps_stream_t stream);
+int ps_lsh_encode_planes(const float *x, int64_t N, int D, const void *staged, int nbits, uint8_t *codes, void *planes,
+                         ps_stream_t stream);
 
 /* Hamming k-NN over all codes: k smallest by (distance, id), ascending; id = row + id_offset.
  * dist int32[nq,k] (INT32_MAX pad), ids int64[nq,k] (-1 pad).  cs = bytes per code (multiple of 4). */

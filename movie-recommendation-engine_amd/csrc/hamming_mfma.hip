@@ -49,6 +49,7 @@
 // every tile.  Asking only for the room the next append needs, and compacting by bisection when a column really is full, took the
 // 256-bit collect pass from 153 to ~100 us (random codes: 94; the straight-line pipeline and the leaner keys are the rest of it).
 #include "ps_select.h"
+#include "lsh_planes.h"
 #include <type_traits>
 
 namespace {
@@ -100,15 +101,7 @@ template <int KS, bool DB> constexpr int ring_bytes() {
 }
 constexpr size_t column_bytes(int cap) { return (size_t)WAVES * cap * 64 * sizeof(uint32_t); }
 
-// ---- sign planes ------------------------------------------------------------------------------------------------
-// 32 code bits -> 32 fp4 nibbles: bit b -> +1 (0x2) / -1 (0xA) = 0xA ^ (b << 3); four bits are spread to the nibble positions
-// 0, 4, 8, 12 by OR-ing shifted copies (a multiply would carry between the overlapping copies)
-__device__ __forceinline__ uint4 expand_word(uint32_t bits) {
-    auto four = [](uint32_t n) { return (n | (n << 3) | (n << 6) | (n << 9)) & 0x1111u; };
-    auto eight = [&](uint32_t byte) { return 0xaaaaaaaau ^ ((four(byte & 15u) | (four(byte >> 4) << 16)) << 3); };
-    return make_uint4(eight(bits & 255u), eight((bits >> 8) & 255u), eight((bits >> 16) & 255u), eight(bits >> 24));
-}
-
+// ---- sign planes (expand_word: lsh_planes.h) --------------------------------------------------------------------
 // one thread = one 16-byte piece (tile, step, lane): the 32 code bits of word 2 s + (lane >> 5) as 32 fp4 nibbles
 __global__ __launch_bounds__(256) void lsh_expand_kernel(const uint32_t *__restrict__ codes, int64_t n, int KS,
                                                          int64_t pieces, uint4 *__restrict__ planes) {

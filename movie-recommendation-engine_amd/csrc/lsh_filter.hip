@@ -21,9 +21,13 @@
 // themselves, for launches of too few rows to fill the CUs with 128-row tiles).  A wave keeps the fragments of its 32 rows for
 // the whole of D in registers (D <= 256: 128 VGPRs), the slabs pass through LDS once per tile (512 KiB of L2 reads per 128
 // rows = 21 B/clk/CU at the MFMA rate), the next slab is prefetched into registers under the MFMAs of the current one.  Sign and
-// flag words collect in LDS; after the last slab the flagged dots are compacted into an LDS list and drained by all 256
-// threads, round after round until no flag is left (the list's size bounds a round, never the number of flagged dots).
+// flag words collect in LDS, and every wave notes which of its flag words have a bit set; after the last slab the noted words
+// become the list of flagged dots without a pass over all flag words, and all 256 threads drain it (128-row tiles: operands
+// through LDS in coalesced pieces of 16 k).  Scan rounds over the flag words follow only while flags are left (the list's size
+// bounds a round, never the number of flagged dots).  ps_lsh_encode_planes also writes the sign planes of the tile's rows
+// (csrc/hamming_mfma.hip: ps_lsh_expand) from the words in LDS.
 #include "ps_common.h"
+#include "lsh_planes.h"
 
 #ifndef PS_LSHF_DEBUG
 #define PS_LSHF_DEBUG 0    // 1: every estimate f is also written to the [N, nbits] float buffer given to ps_debug_lsh_dump
@@ -127,18 +131,30 @@ struct FilterArgs {
     uint32_t *codes;
     unsigned long long *counters;       // nullptr: no statistics
     float c;
+    uint4 *planes;                      // nullptr: codes only; else the sign planes of the codes (layout: csrc/hamming_mfma.hip)
+    int64_t plane_pieces;               // 16-byte pieces of the plane table, padding tiles included
 };
+
+// float4s of the first LDS area: the slabs of an iteration during the sweep; in the 128-row form (JS = 1) then the piece
+// buffer of the chains, 256 entries x 2 operands x 64 bytes = 32 KiB whatever D is, so the area is at least that there (D < 256:
+// the slab alone is smaller).  The 64-row form has no piece buffer and keeps its two slabs.
+__host__ __device__ constexpr int area_f4(int KS, int JS) {
+    return JS == 1 && slab_f4(KS) < 2048 ? 2048 : JS * slab_f4(KS);
+}
 
 template <int KS, int JS>
 __global__ __launch_bounds__(256, JS == 1 ? 2 : 1) void lsh_filter_kernel(const FilterArgs g) {
     constexpr int D = KS * 16, ROWS = 128 / JS, RG = 4 / JS, SF4 = slab_f4(KS), NQ = KS / 2;
+    constexpr int PF = KS >= 16 ? 4 : 2;                                      // chain pieces in flight
     extern __shared__ f32x4 lds[];
-    __shared__ uint32_t cnt, more;
+    constexpr int SEG = LIST_CAP / 4;                                          // flagged words a wave notes during the sweep
+    __shared__ uint32_t cnt, more, segn[4];
     const int W = g.nbits / 32;
     f32x4 *slabL = lds;                                                       // JS slabs
-    uint32_t *codesL = reinterpret_cast<uint32_t *>(lds + JS * SF4);           // [W][ROWS] sign words
+    uint32_t *codesL = reinterpret_cast<uint32_t *>(lds + area_f4(KS, JS));    // [W][ROWS] sign words
     uint32_t *flagsL = codesL + W * ROWS;                                      // [W][ROWS] flag words
     uint32_t *listL = flagsL + W * ROWS;                                       // [LIST_CAP]
+    uint16_t *wordL = reinterpret_cast<uint16_t *>(listL + LIST_CAP);          // [4][SEG] flag words with a bit set, per wave
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
@@ -187,6 +203,11 @@ __global__ __launch_bounds__(256, JS == 1 ? 2 : 1) void lsh_filter_kernel(const 
         }                                                                               \
     }
     LSHF_PREFETCH(0)
+    if (tid == 0) {                                                            // published by the barrier at the top of the sweep
+        cnt = 0u;
+        more = 0u;
+    }
+    int wcnt = 0;                                                              // flag words with a bit set, this wave (uniform)
     LSHF_STAMP(1);
     [[maybe_unused]] unsigned long long t_stage = 0ull, t_mfma = 0ull, t_epi = 0ull;    // PS_LSHF_DEBUG == 2 only
     for (int it = 0; it < iters; ++it) {
@@ -264,6 +285,18 @@ __global__ __launch_bounds__(256, JS == 1 ? 2 : 1) void lsh_filter_kernel(const 
             if (!live) fm = 0u;                                                // rows past N: no chain, nothing stored
             sm |= (uint32_t)__shfl_xor((int)sm, 32);
             fm |= (uint32_t)__shfl_xor((int)fm, 32);
+            // a word with a flag set is noted as it is found, in the wave's own run of wordL and counted in a register: a
+            // handful of instructions per slab, no atomic, nothing to wait for (the sweep is bound by instruction issue, and
+            // an LDS round trip in front of its barriers costs more than the scan it saves).  Words beyond the run stay for
+            // the scan rounds after the sweep.
+            const bool fw = h == 0 && fm != 0u;
+            const unsigned long long wm = __ballot(fw);
+            if (fw) {
+                const int at = wcnt + (int)__builtin_amdgcn_mbcnt_lo((uint32_t)wm, 0u);
+                if (at < SEG) wordL[wave * SEG + at] = (uint16_t)(jt * ROWS + rg * 32 + r);
+                else more = 1u;
+            }
+            wcnt += __builtin_popcountll(wm);
             if (h == 0) {
                 codesL[jt * ROWS + rg * 32 + r] = sm;
                 flagsL[jt * ROWS + rg * 32 + r] = fm;
@@ -273,16 +306,128 @@ __global__ __launch_bounds__(256, JS == 1 ? 2 : 1) void lsh_filter_kernel(const 
     }
 
 #undef LSHF_PREFETCH
+    if (lane == 0) segn[wave] = (uint32_t)(wcnt < SEG ? wcnt : SEG);
     LSHF_STAMP(2);
     LSHF_PUT(6, t_stage);
     LSHF_PUT(7, t_mfma);
     LSHF_PUT(8, t_epi);
 
-    // ---- the flagged dots: compact up to LIST_CAP of them, run their chains, repeat until no flag is left
+    // ---- the flagged dots.  The sweep has noted the words that hold them: one thread per noted word lists its first flag at
+    // the word's own place in the list (no reservation) and, rarely, appends further ones behind all first flags with an atomic.
+    // Their chains run now; only if a wave noted more words than its run takes, or the list more dots than LIST_CAP, do scan
+    // rounds over all flag words follow, until no flag is left.
+    //
+    // A round of chains takes 256 list entries, one per thread, and moves the operands in pieces of 16 consecutive k: four
+    // adjacent lanes load the four float4s of ONE entry's x piece (then of its A piece), so a wave load touches 16 runs of
+    // 64 bytes and not 64 cache lines; the pieces pass through LDS (the slab area, dead by now) to the thread that owns the
+    // chain, which runs acc = fmaf(x[k], A[j][k], acc) in k order as before.  PF pieces are in flight ahead of the fmas.
+    // Entry e keeps float4 q of a piece at 4 e + (q ^ ((e >> 2) & 3)): conflict-free for the loaders' stores and for the
+    // owners' reads.  Slots past the round's last entry repeat its first one: no address outside the listed rows is formed,
+    // and the loads stay unconditional, so that the compiler counts them (vmcnt) and a store waits for its own piece only.
+    // The 64-row form (JS = 2) keeps one thread per chain reading its own rows: a tile has about a hundred flagged dots
+    // there, on a CU that holds no second workgroup, and its chains phase measured shorter that way.
     const int nwords = W * ROWS;
+    const f32x4 *xb = reinterpret_cast<const f32x4 *>(g.x + row0 * D), *ab = reinterpret_cast<const f32x4 *>(g.a32);
+    f32x4 *pieceL = lds;
     unsigned long long nflag = 0ull;
+    __syncthreads();
+    const int s1 = (int)segn[0], s2 = s1 + (int)segn[1], s3 = s2 + (int)segn[2];   // where the runs of waves 1, 2, 3 begin
+    const int nw = s3 + (int)segn[3];
+    for (int e = tid; e < nw; e += 256) {
+        const int w = (e >= s1 ? 1 : 0) + (e >= s2 ? 1 : 0) + (e >= s3 ? 1 : 0);
+        const uint32_t idx = wordL[w * SEG + e - (w == 3 ? s3 : w == 2 ? s2 : w == 1 ? s1 : 0)];
+        uint32_t m = flagsL[idx];
+        listL[e] = idx * 32u + (uint32_t)__builtin_ctz(m);
+        m &= m - 1u;
+        if (m != 0u) {
+            uint32_t pos = (uint32_t)nw + atomicAdd(&cnt, (uint32_t)__builtin_popcount(m));
+            while (m != 0u && pos < (uint32_t)LIST_CAP) {
+                listL[pos++] = idx * 32u + (uint32_t)__builtin_ctz(m);
+                m &= m - 1u;
+            }
+            if (m != 0u) more = 1u;
+        }
+        flagsL[idx] = m;
+    }
+    __syncthreads();
+    int n = (uint32_t)nw + cnt < (uint32_t)LIST_CAP ? nw + (int)cnt : LIST_CAP;
+    bool again = more != 0u;
+    LSHF_STAMP(3);
     for (;;) {
-        __syncthreads();
+        if constexpr (JS == 2) {
+            for (int e = tid; e < n; e += 256) {
+                const uint32_t ent = listL[e];
+                const int idx = (int)(ent >> 5), b = (int)(ent & 31u);
+                const f32x4 *xr = xb + (idx % ROWS) * (D / 4), *ar = ab + ((idx / ROWS) * 32 + b) * (D / 4);
+                float acc = 0.f;
+#pragma unroll 16
+                for (int k = 0; k < D / 4; ++k) {
+                    const f32x4 u = xr[k], v = ar[k];
+                    acc = fmaf(u[0], v[0], acc);
+                    acc = fmaf(u[1], v[1], acc);
+                    acc = fmaf(u[2], v[2], acc);
+                    acc = fmaf(u[3], v[3], acc);
+                }
+                if (acc >= 0.f) atomicOr(&codesL[idx], 1u << b);
+            }
+        }
+        for (int base = 0; JS == 1 && base < n; base += 256) {
+            const int m = n - base < 256 ? n - base : 256;
+            const int q = tid & 3, sw = (tid >> 4) & 3;
+            int xo[4], ao[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int el = 64 * i + (tid >> 2);
+                const uint32_t ent = listL[base + (el < m ? el : 0)];
+                const int idx = (int)(ent >> 5), b = (int)(ent & 31u);
+                xo[i] = (idx % ROWS) * (D / 4) + q;
+                ao[i] = ((idx / ROWS) * 32 + b) * (D / 4) + q;
+            }
+            const uint32_t mine = listL[base + (tid < m ? tid : 0)];
+            f32x4 px[PF][4], pa[PF][4];
+#pragma unroll
+            for (int p = 0; p < PF; ++p) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    px[p][i] = xb[xo[i] + 4 * p];
+                    pa[p][i] = ab[ao[i] + 4 * p];
+                }
+            }
+            float acc = 0.f;
+#pragma unroll
+            for (int p = 0; p < KS; ++p) {
+                __syncthreads();                                               // the piece before (the slabs, the last round) is read
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int at = (64 * i + (tid >> 2)) * 4 + (q ^ sw);
+                    pieceL[at] = px[p % PF][i];
+                    pieceL[1024 + at] = pa[p % PF][i];
+                }
+                __syncthreads();
+                if (p + PF < KS) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        px[p % PF][i] = xb[xo[i] + 4 * (p + PF)];
+                        pa[p % PF][i] = ab[ao[i] + 4 * (p + PF)];
+                    }
+                }
+                if (tid < m) {
+                    const int so = (tid >> 2) & 3;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const f32x4 u = pieceL[tid * 4 + (j ^ so)], v = pieceL[1024 + tid * 4 + (j ^ so)];
+                        acc = fmaf(u[0], v[0], acc);
+                        acc = fmaf(u[1], v[1], acc);
+                        acc = fmaf(u[2], v[2], acc);
+                        acc = fmaf(u[3], v[3], acc);
+                    }
+                }
+            }
+            if (tid < m && acc >= 0.f) atomicOr(&codesL[mine >> 5], 1u << (mine & 31u));
+        }
+        nflag += (unsigned long long)n;
+        if (!again) break;
+        __syncthreads();                                                       // the list, cnt and more are read
         if (tid == 0) {
             cnt = 0u;
             more = 0u;
@@ -290,12 +435,12 @@ __global__ __launch_bounds__(256, JS == 1 ? 2 : 1) void lsh_filter_kernel(const 
         __syncthreads();
         // a thread counts the flags of its words, reserves that many list slots with ONE atomic and fills those below LIST_CAP;
         // flags that found no slot stay set for the next round
-        int mine = 0;
+        int own = 0;
 #pragma unroll 4
-        for (int idx = tid; idx < nwords; idx += 256) mine += __builtin_popcount(flagsL[idx]);
-        if (mine > 0) {
-            uint32_t pos = atomicAdd(&cnt, (uint32_t)mine);
-            if (pos + (uint32_t)mine > (uint32_t)LIST_CAP) more = 1u;
+        for (int idx = tid; idx < nwords; idx += 256) own += __builtin_popcount(flagsL[idx]);
+        if (own > 0) {
+            uint32_t pos = atomicAdd(&cnt, (uint32_t)own);
+            if (pos + (uint32_t)own > (uint32_t)LIST_CAP) more = 1u;
             for (int idx = tid; idx < nwords && pos < (uint32_t)LIST_CAP; idx += 256) {
                 uint32_t m = flagsL[idx];
                 if (m == 0u) continue;
@@ -307,28 +452,8 @@ __global__ __launch_bounds__(256, JS == 1 ? 2 : 1) void lsh_filter_kernel(const 
             }
         }
         __syncthreads();
-        LSHF_STAMP(3);
-        const int n = cnt < (uint32_t)LIST_CAP ? (int)cnt : LIST_CAP;
-        const bool again = more != 0u;
-        for (int e = tid; e < n; e += 256) {
-            const uint32_t ent = listL[e];
-            const int idx = (int)(ent >> 5), b = (int)(ent & 31u);
-            const int jt = idx / ROWS, rl = idx % ROWS;
-            const float4 *xr = reinterpret_cast<const float4 *>(g.x + (row0 + rl) * D);
-            const float4 *ar = reinterpret_cast<const float4 *>(g.a32 + (size_t)(jt * 32 + b) * D);
-            float acc = 0.f;
-#pragma unroll 16
-            for (int k = 0; k < D / 4; ++k) {
-                const float4 u = xr[k], v = ar[k];
-                acc = fmaf(u.x, v.x, acc);
-                acc = fmaf(u.y, v.y, acc);
-                acc = fmaf(u.z, v.z, acc);
-                acc = fmaf(u.w, v.w, acc);
-            }
-            if (acc >= 0.f) atomicOr(&codesL[idx], 1u << b);
-        }
-        nflag += (unsigned long long)n;
-        if (!again) break;
+        n = cnt < (uint32_t)LIST_CAP ? (int)cnt : LIST_CAP;
+        again = more != 0u;
     }
     __syncthreads();
     LSHF_STAMP(4);
@@ -337,6 +462,21 @@ __global__ __launch_bounds__(256, JS == 1 ? 2 : 1) void lsh_filter_kernel(const 
     for (int i = tid; i < nwords; i += 256) {
         const int rl = i / W, w = i % W;
         if (row0 + rl < g.N) g.codes[(row0 + rl) * W + w] = codesL[w * ROWS + rl];
+    }
+    // ---- and their sign planes: piece (tile * W / 2 + s) * 64 + lane = word 2 s + (lane >> 5) of row 32 tile + (lane & 31),
+    // zero for rows past N; the last workgroup also zeroes the padding tiles behind the last tile of the grid
+    if (g.planes != nullptr) {
+        const int KP = W / 2;
+        const int64_t first = (int64_t)blockIdx.x * (ROWS / 32) * KP * 64;
+        for (int i = tid; i < nwords; i += 256) {
+            const int ln = i & 63, ts = i >> 6;
+            const int rl = (ts / KP) * 32 + (ln & 31), w = 2 * (ts % KP) + (ln >> 5);
+            uint4 o = make_uint4(0u, 0u, 0u, 0u);
+            if (row0 + rl < g.N) o = expand_word(codesL[w * ROWS + rl]);
+            if (first + i < g.plane_pieces) g.planes[first + i] = o;
+        }
+        if (blockIdx.x == gridDim.x - 1)
+            for (int64_t i = first + nwords + tid; i < g.plane_pieces; i += 256) g.planes[i] = make_uint4(0u, 0u, 0u, 0u);
     }
     if (g.counters != nullptr && tid == 0) {
         const int64_t rows = g.N - row0 < ROWS ? g.N - row0 : ROWS;
@@ -348,7 +488,7 @@ __global__ __launch_bounds__(256, JS == 1 ? 2 : 1) void lsh_filter_kernel(const 
 
 template <int KS, int JS>
 size_t filter_lds(int nbits) {
-    return (size_t)JS * slab_f4(KS) * 16 + (size_t)(nbits / 32) * (128 / JS) * 8 + (size_t)LIST_CAP * 4;
+    return (size_t)area_f4(KS, JS) * 16 + (size_t)(nbits / 32) * (128 / JS) * 8 + (size_t)LIST_CAP * 4 + (size_t)LIST_CAP * 2;
 }
 
 template <int KS, int JS>
@@ -384,7 +524,8 @@ extern "C" int ps_lsh_stage(const float *A, int nbits, int D, void *staged, size
 }
 
 // ps_lsh_encode with PS_LSH_STAGED (csrc/dense_mfma.hip checks N, D, nbits, the pointers and the flag combination)
-int psi_lsh_encode_staged(const float *x, int64_t N, int D, const void *staged, int nbits, uint8_t *codes, ps_stream_t stream) {
+static int encode_staged(const float *x, int64_t N, int D, const void *staged, int nbits, uint8_t *codes, void *planes,
+                         size_t planes_bytes, ps_stream_t stream) {
     if (!served(nbits, D) || (reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(staged)) % 16 != 0) return PS_EUNSUPPORTED;
     static PsPerDevice cus;                                                    // attributes set, CU count known
     int dv = 0;
@@ -409,6 +550,8 @@ int psi_lsh_encode_staged(const float *x, int64_t N, int D, const void *staged, 
     g.codes = reinterpret_cast<uint32_t *>(codes);
     g.counters = se && atoi(se) != 0 ? reinterpret_cast<unsigned long long *>(const_cast<unsigned char *>(img) + 16) : nullptr;
     g.c = 0x1p-12f * (D > 256 ? (float)D / 256.f : 1.f);
+    g.planes = static_cast<uint4 *>(planes);
+    g.plane_pieces = (int64_t)(planes_bytes / 16);
     // 64-row tiles while 128-row tiles would leave half the CUs without one: twice the workgroups, each half as long.
     // PS_LSH_ROWS=64 / 128 forces a tile (tests run both)
     const int rows = re ? atoi(re) : 0;
@@ -420,4 +563,19 @@ int psi_lsh_encode_staged(const float *x, int64_t N, int D, const void *staged, 
         case 8: return half ? launch_filter<8, 2>(g, st) : launch_filter<8, 1>(g, st);
         default: return half ? launch_filter<16, 2>(g, st) : launch_filter<16, 1>(g, st);
     }
+}
+
+int psi_lsh_encode_staged(const float *x, int64_t N, int D, const void *staged, int nbits, uint8_t *codes, ps_stream_t stream) {
+    return encode_staged(x, N, D, staged, nbits, codes, nullptr, 0, stream);
+}
+
+// the staged ps_lsh_encode and ps_lsh_expand of its codes in one launch: a workgroup writes the planes of its rows from the
+// sign words it still holds in LDS
+extern "C" int ps_lsh_encode_planes(const float *x, int64_t N, int D, const void *staged, int nbits, uint8_t *codes, void *planes,
+                                    ps_stream_t stream) {
+    if (N < 0 || D <= 0 || nbits <= 0 || !x || !staged || !codes || !planes) return PS_EINVAL;
+    const size_t planes_bytes = ps_lsh_planes_bytes(N, nbits / 8);
+    if (planes_bytes == 0 || nbits % 64 != 0 || !served(nbits, D)) return PS_EUNSUPPORTED;
+    if (reinterpret_cast<size_t>(codes) % 4 != 0 || reinterpret_cast<size_t>(planes) % 16 != 0) return PS_EUNSUPPORTED;
+    return encode_staged(x, N, D, staged, nbits, codes, planes, planes_bytes, stream);
 }

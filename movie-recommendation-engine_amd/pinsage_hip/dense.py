@@ -276,9 +276,10 @@ def gcn_layer(x, W, b, h_full, ids, counts, nvalid, W2, wts=None, max_idx=None, 
     return linear(x, W, b, x2=h_neigh, W2=W2, relu=relu, l2norm=l2norm)
 
 
-def lsh_encode(x, A):
+def lsh_encode(x, A, planes=False):
     """codes uint8[n, nbits/8]: bit j = (x . A[j] >= 0), LSB first (faiss IndexLSH.sa_encode).  A: matrix, StagedWeight or
-    StagedLsh."""
+    StagedLsh.  planes=True: -> (codes, lsh_expand(codes)), from the encode launch itself where ps_lsh_encode_planes serves
+    the call (a StagedLsh, whole 64-bit code words), else as the two launches."""
     flags = nv.PS_LSH_STAGED if isinstance(A, StagedLsh) else nv.PS_WPERM if isinstance(A, StagedWeight) else 0
     if flags == nv.PS_LSH_STAGED:
         nbits, da, A = A.shape[0], A.shape[1], A.image
@@ -293,9 +294,17 @@ def lsh_encode(x, A):
     if da != d:
         raise ValueError("projection matrix must be [nbits, dim]")
     codes = torch.empty((n, nbits // 8), dtype=torch.uint8, device=x.device)
+    if planes and flags == nv.PS_LSH_STAGED:
+        pl, nb = nv.workspace("ps_lsh_planes_bytes", x.device, n, nbits // 8)
+        if nb:
+            with torch.cuda.device(x.device):
+                rc = nv.call("ps_lsh_encode_planes", nv.ptr(x), n, d, nv.ptr(A), nbits, nv.ptr(codes), nv.ptr(pl), nv.stream(),
+                             unsupported_ok=True)
+            if rc == nv.PS_OK:
+                return codes, pl
     with torch.cuda.device(x.device):
         nv.call("ps_lsh_encode", nv.ptr(x), n, d, nv.ptr(A), nbits, nv.ptr(codes), flags, nv.stream())
-    return codes
+    return (codes, lsh_expand(codes)) if planes else codes
 
 
 HAMMING_MAX_K = 64        # ps_hamming_topk (popcount scan); the MFMA scan serves k <= 32; beyond 64: _hamming_topk_large_k

@@ -85,6 +85,7 @@ PROTOTYPES = {
     "ps_lsh_stage_bytes": "z ii",
     "ps_lsh_stage": "i piipzp",
     "ps_lsh_encode": "i pqipipip",
+    "ps_lsh_encode_planes": "i pqipippp",
     "ps_hamming_topk_workspace_bytes": "z qqii",
     "ps_hamming_topk": "i pqpqiiqpppzp",
     "ps_lsh_planes_bytes": "z qi",
@@ -176,8 +177,13 @@ def set_timer(t):
     _timer = t
 
 
-def call(name, *args):
-    """Invoke one C-ABI entry point and raise on a non-zero status."""
+# entry points that the per-launch timer books under another call's name: the encode that also writes the planes is an encode
+_TIMER_NAMES = {"ps_lsh_encode_planes": "ps_lsh_encode"}
+
+
+def call(name, *args, unsupported_ok=False):
+    """Invoke one C-ABI entry point and raise on a non-zero status.  Returns the status, which is therefore always PS_OK --
+    unless unsupported_ok is set: then PS_EUNSUPPORTED is returned, not raised, for a caller that has another way."""
     fn = getattr(lib(), name)
     if _timer is None:
         rc = fn(*args)
@@ -186,8 +192,11 @@ def call(name, *args):
         a.record()
         rc = fn(*args)
         b.record()
-        _timer.events.append((name, a, b))
+        _timer.events.append((_TIMER_NAMES.get(name, name), a, b))
+    if unsupported_ok and rc == PS_EUNSUPPORTED:
+        return rc
     check(rc, name)
+    return rc
 
 
 def ptr(t, contiguous=True):

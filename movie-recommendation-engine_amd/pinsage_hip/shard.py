@@ -174,6 +174,10 @@ class HipOps:
     def lsh_encode(self, x, A):
         return dense.lsh_encode(x, A)
 
+    def lsh_encode_planes(self, x, A):
+        """(codes, their sign planes) from one launch where the encode serves it (dense.lsh_encode, planes=True)"""
+        return dense.lsh_encode(x, A, planes=True)
+
     def stage_weight(self, W):
         return dense.stage_weight(W)
 
@@ -365,12 +369,18 @@ class ShardedPinSage:
 
     def build_index(self, emb_local, A):
         self.A = A
+        # sign planes of the scanned code table for the fp4-MFMA scan (backends without them scan the packed codes): where
+        # the table is this rank's own codes they come out of the encode launch, of a gathered table from a pass over it
+        if hasattr(self.ops, "lsh_encode_planes") and (self.world == 1
+                                                       or self.M * (int(A.shape[0]) // 8) > self.REPLICATE_CODES_BYTES):
+            self.codes, self.planes = self.ops.lsh_encode_planes(emb_local, self._staged_A(A))
+            self.codes_all = None
+            return self.codes
         self.codes = self.ops.lsh_encode(emb_local, self._staged_A(A))
         self.codes_all = None
         if self.world > 1 and self.M * int(self.codes.size(1)) <= self.REPLICATE_CODES_BYTES:
             self.codes_all = self.comm.gather_rows(self.codes, self.chunk, "codes")[: self.M]
         scanned = self.codes_all if self.codes_all is not None else self.codes
-        # sign planes of the scanned code table for the fp4-MFMA scan (backends without them scan the packed codes)
         self.planes = self.ops.lsh_planes(scanned) if hasattr(self.ops, "lsh_planes") else None
         return self.codes
 
