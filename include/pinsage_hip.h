@@ -509,6 +509,40 @@ int ps_ivf_topk(const float *X, int64_t N, int D, const int64_t *list_ptr, int n
 int ps_spmm_csr(const int64_t *rowptr, const int32_t *col, const float *val, const float *x, int64_t N, int H,
                 int64_t V, int64_t E, float *out, ps_stream_t stream);
 
+/* ---- the same aggregation for training (pinsage_hip/graph.py: SpmmFn), csrc/spmm_exact.hip: an SpMM whose every output bit is a
+ * function of its inputs, and the per-edge row dot that is the gradient of its edge values.  Caller-allocated buffers, no
+ * allocation, no synchronisation, no float atomics.  PS_OK for an empty problem (V == 0; E == 0 zeroes out and leaves d
+ * untouched), whatever the pointers; PS_EINVAL for a non-positive H, a negative size, a null pointer on a non-empty problem or a
+ * short workspace; PS_EUNSUPPORTED where the grid would overflow (more than 2^31 - 1 slices).  The workspace is not preserved
+ * between calls and needs no alignment.  rowptr int64[V+1] / col int32[E] as for ps_spmm_csr: rowptr[0] = 0, non-decreasing,
+ * rowptr[V] = E.
+ *
+ * ps_spmm_csr_exact: the inputs of ps_spmm_csr (val float[E] or NULL = 1.0f, x float[N,H], out float[V,H]).
+ *   Slices.  The edge slots are cut into slices [k S, (k + 1) S), S = ps_spmm_exact_slice() (a compile-time constant, 512).  The
+ *   slot range [rowptr[r], rowptr[r+1]) of row r is cut by those slices into consecutive pieces.
+ *   A piece is the chain acc = fmaf(val[e], x[col[e], c], acc) over its slots e ascending, from +0.0; a slot whose source id
+ *   col[e] lies outside [0, N) is skipped (no operation; x is never read there).
+ *   out[r, c] = ((p_0 + p_1) + p_2) + ... over the row's pieces in ascending order; p_0 alone for a row with one piece; +0.0 for
+ *   an empty row.  Every element of out is written.
+ *   The gradient of out with respect to x is the same entry point over the edges grouped by SOURCE node (rowptr / col = target
+ *   node, val carried to that slot order) with the gradient of out as the feature matrix.
+ *   workspace: ps_spmm_csr_exact_workspace_bytes(E, H) (two rows of H floats per slice; 0 for E <= 0 or H <= 0).  Two launches
+ *   after a fill of out with zeros: one wave per slice (a piece that is a whole row goes straight to out, any other piece to the
+ *   workspace with plain stores), then the sums of the cut rows, one wave per row.
+ *
+ * ps_sddmm_csr: the gradient of out with respect to val.  g float[V,H] (the gradient of out), d float[E] in CSR slot order: for
+ *   slot e of row r, d[e] = sum_c g[r,c] x[col[e],c] in the arithmetic of ps_attention_bwd_rows' da: lane l chains
+ *   part = fmaf(g[r,c], x[id,c], part) over its columns c = 64 VEC k + VEC l + e (sweep k and element e ascending) from +0.0, columns
+ *   past H entering as 0 * 0; VEC = 4 when H % 4 == 0 and x, g are 16-byte aligned, else 1; the 64 lanes are then added by the
+ *   balanced tree of ps_attention_weights (lanes 2 i and 2 i + 1 first).  A source id outside [0, N) gives +0.0 and x is not read.
+ *   One launch, one wave per slice of S slots; every element of d is written. */
+int ps_spmm_exact_slice(void);
+size_t ps_spmm_csr_exact_workspace_bytes(int64_t E, int H);
+int ps_spmm_csr_exact(const int64_t *rowptr, const int32_t *col, const float *val, const float *x, int64_t N, int H,
+                      int64_t V, int64_t E, float *out, void *workspace, size_t workspace_bytes, ps_stream_t stream);
+int ps_sddmm_csr(const int64_t *rowptr, const int32_t *col, const float *x, int64_t N, const float *g, int64_t V, int H,
+                 int64_t E, float *d, ps_stream_t stream);
+
 /* ---- GraphBuilder.build_item_similarity_graph (data/graph_builder.py:59-116): the item co-occurrence graph.
  * m_ua = number of rating rows (user u, item a); users are RANKS 0..U-1 in the reference's groupby('userId') order.
  * count(a, b) = sum_u m_ua m_ub (a < b), count(a, a) = sum_u m_ua (m_ua - 1) / 2: an integer GEMM A A^T over K = users,

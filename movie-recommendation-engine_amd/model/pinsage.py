@@ -11,8 +11,10 @@ What runs where
         bias/ReLU/concat/L2-normalise fused); with autograd enabled the same kernel does the
         pooling forward and torch does the (differentiable) dense layers.
   MLP branch (:205-214, what train.py uses)           -> plain torch nn.Linear (autograd), as in the reference.
-  edge_index branch (:243-245, GraphConv)             -> ps_spmm_csr over the edges grouped by target node (no grad),
-        torch index_add_ when autograd is needed.
+  edge_index branch (:243-245, GraphConv)             -> ps_spmm_csr over the edges grouped by target node (no grad); under
+        autograd ps_spmm_csr_exact forward, the same kernel over the source-grouped edges and ps_sddmm_csr backward
+        (pinsage_hip.graph.spmm: no float atomics, no [E, H] tensor); sampling.grad_method = "torch" and CPU tensors keep
+        torch's x[src] / index_add_.
 """
 from __future__ import annotations
 
@@ -73,19 +75,29 @@ class GraphConv(nn.Module):
                                                              any(p.requires_grad for p in self.parameters()))):
             # inference on the GPU: CSR row gather-reduce (ps_spmm_csr) over the edges grouped by target node
             tc = _target_csr(edge_index, int(x.size(0)))
-            val = None
-            if edge_weight is not None or importance_weights is not None:
-                w = torch.ones(tc.E, dtype=torch.float32, device=x.device)
-                if edge_weight is not None:
-                    w = w * edge_weight.to(x.device).float().view(-1)
-                if importance_weights is not None:
-                    w = w * importance_weights.to(x.device).float().view(-1)
-                val = w[tc.perm].contiguous()
-            return graph_mod.spmm_csr(tc, x.float(), val)
+            return graph_mod.spmm_csr(tc, x.float(), self._slot_values(tc, x.device, edge_weight, importance_weights))
+        if x.is_cuda and x.dtype == torch.float32 and graph_mod.use_hip_grad(x):
+            # training on the GPU: the exact SpMM and its HIP backward; the weights reach slot order through differentiable torch
+            # operations, so torch carries their gradient back to the edge order
+            tc = _target_csr(edge_index, int(x.size(0)))
+            return graph_mod.spmm(tc, x, self._slot_values(tc, x.device, edge_weight, importance_weights))
         src, dst = edge_index[0], edge_index[1]
         msg = self.message(x[src], edge_weight=edge_weight, importance_weights=importance_weights)
         out = torch.zeros_like(x)
         return out.index_add_(0, dst, msg)
+
+    @staticmethod
+    def _slot_values(tc, device, edge_weight, importance_weights):
+        """edge_weight * importance_weights in the slot order of a TargetCSR (None: every edge counts 1).  perm is a permutation,
+        so the gather's backward (index_add_ into zeros) puts every gradient into a slot of its own: exact, no sort"""
+        w = None
+        for t in (edge_weight, importance_weights):
+            if t is not None:
+                t = t.to(device).float().view(-1)
+                w = t if w is None else w * t
+        if w is None:
+            return None
+        return (w if w.numel() == tc.E else w.expand(tc.E)).index_select(0, tc.perm)
 
     def message(self, x_j, edge_weight=None, importance_weights=None):
         msg = x_j

@@ -132,6 +132,27 @@ class DeviceGraph:
                                                          self.buckets, self.dest_info) if t is not None)
 
 
+def _csr_with_perm(rows, cols, E, V, dev):
+    """(rowptr int64[V+1], col int32[E], perm int64[E]) of the edges (rows[e], cols[e]) grouped by row with ps_csr_build's
+    stable sort: col = cols in slot order, perm = the position of every slot in the original edge order."""
+    rowptr = torch.empty(V + 1, dtype=torch.int64, device=dev)
+    col = torch.empty(E, dtype=torch.int32, device=dev)
+    order = torch.empty(E, dtype=torch.float64, device=dev)
+    ws, wsb = nv.workspace("ps_csr_build_workspace_bytes", dev, E, V)
+    # the "weight" channel carries the original edge number (exact in fp32 only below 2^24, so it is passed
+    # through the fp64 output by building it in two halves)
+    idx = torch.arange(E, device=dev)
+    lo16 = (idx & 0xFFFF).to(torch.float32).contiguous()
+    hi16 = (idx >> 16).to(torch.float32).contiguous()
+    with torch.cuda.device(dev):
+        nv.call("ps_csr_build", nv.ptr(rows), nv.ptr(cols), nv.ptr(lo16), E, V, nv.ptr(rowptr), nv.ptr(col),
+                nv.ptr(order), nv.ptr(ws), wsb, nv.stream())
+        lo_sorted = order.clone()
+        nv.call("ps_csr_build", nv.ptr(rows), nv.ptr(cols), nv.ptr(hi16), E, V, nv.ptr(rowptr), nv.ptr(col),
+                nv.ptr(order), nv.ptr(ws), wsb, nv.stream())
+    return rowptr, col, (order.to(torch.int64) << 16) | lo_sorted.to(torch.int64)
+
+
 class TargetCSR:
     """Edges grouped by target node (what GraphConv.propagate aggregates over): rowptr / col (= source node) /
     perm (position of every CSR slot in the original edge order, for per-edge weights).  Built with the same
@@ -152,22 +173,27 @@ class TargetCSR:
                                  "(global ids passed with batch-local features?)")
         src, dst = ei[0].contiguous(), ei[1].contiguous()
         self.V, self.E, self.device = V, E, dev
-        self.rowptr = torch.empty(V + 1, dtype=torch.int64, device=dev)
-        self.col = torch.empty(E, dtype=torch.int32, device=dev)
-        order = torch.empty(E, dtype=torch.float64, device=dev)
-        ws, wsb = nv.workspace("ps_csr_build_workspace_bytes", dev, E, V)
-        # the "weight" channel carries the original edge number (exact in fp32 only below 2^24, so it is passed
-        # through the fp64 output by building it in two halves)
-        idx = torch.arange(E, device=dev)
-        lo16 = (idx & 0xFFFF).to(torch.float32).contiguous()
-        hi16 = (idx >> 16).to(torch.float32).contiguous()
-        with torch.cuda.device(dev):
-            nv.call("ps_csr_build", nv.ptr(dst), nv.ptr(src), nv.ptr(lo16), E, V, nv.ptr(self.rowptr), nv.ptr(self.col),
-                    nv.ptr(order), nv.ptr(ws), wsb, nv.stream())
-            lo_sorted = order.clone()
-            nv.call("ps_csr_build", nv.ptr(dst), nv.ptr(src), nv.ptr(hi16), E, V, nv.ptr(self.rowptr), nv.ptr(self.col),
-                    nv.ptr(order), nv.ptr(ws), wsb, nv.stream())
-        self.perm = (order.to(torch.int64) << 16) | lo_sorted.to(torch.int64)
+        self.rowptr, self.col, self.perm = _csr_with_perm(dst, src, E, V, dev)
+        self._src, self._dst, self._source = src, dst, None      # the edge rows, kept until source() has grouped them by source
+
+    def source(self):
+        """(SourceCSR, index): the same edges grouped by SOURCE node -- rowptr / col (= target node) / perm, from the same
+        ps_csr_build with the rows of edge_index not swapped -- and the int64 index that carries a vector from this object's
+        slot order to that one's (val_source = val_target[index]; perm is a permutation, so it is one gather).  What the
+        gradient of spmm with respect to the features sweeps; built on first use and kept."""
+        if self._source is None:
+            s = SourceCSR()
+            s.V, s.E, s.device = self.V, self.E, self.device
+            s.rowptr, s.col, s.perm = _csr_with_perm(self._src, self._dst, self.E, self.V, self.device)
+            slot_of_edge = torch.empty_like(self.perm)
+            slot_of_edge[self.perm] = torch.arange(self.E, device=self.device)
+            self._source = (s, slot_of_edge[s.perm])
+            self._src = self._dst = None
+        return self._source
+
+
+class SourceCSR:
+    """The edges of a TargetCSR grouped by source node (TargetCSR.source): V, E, device, rowptr, col (= target node), perm."""
 
 
 def spmm_csr(tcsr, x, val=None):
@@ -178,3 +204,93 @@ def spmm_csr(tcsr, x, val=None):
         nv.call("ps_spmm_csr", nv.ptr(tcsr.rowptr), nv.ptr(tcsr.col), nv.ptr(val), nv.ptr(x), x.size(0), x.size(1), tcsr.V, tcsr.E,
                 nv.ptr(out), nv.stream())
     return out
+
+
+def spmm_csr_exact(csr, x, val=None):
+    """spmm_csr without atomics (ps_spmm_csr_exact): every output bit is a function of the inputs.  csr: a TargetCSR or the
+    SourceCSR of one; x fp32 [N, H] and val fp32 [E] (slot order) contiguous."""
+    N, H = int(x.size(0)), int(x.size(1))
+    out = torch.empty((csr.V, H), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        ws, nbytes = nv.workspace("ps_spmm_csr_exact_workspace_bytes", x.device, csr.E, H)
+        nv.call("ps_spmm_csr_exact", nv.ptr(csr.rowptr), nv.ptr(csr.col), nv.ptr(val), nv.ptr(x), N, H, csr.V, csr.E, nv.ptr(out),
+                nv.ptr(ws), nbytes, nv.stream())
+    return out
+
+
+def sddmm_csr(csr, x, g):
+    """d[e] = g[r] . x[col[e]] for every slot e of row r (ps_sddmm_csr): the gradient of spmm_csr_exact's val.  x fp32 [N, H],
+    g fp32 [V, H] contiguous."""
+    d = torch.empty(csr.E, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        nv.call("ps_sddmm_csr", nv.ptr(csr.rowptr), nv.ptr(csr.col), nv.ptr(x), int(x.size(0)), nv.ptr(g), csr.V, int(x.size(1)),
+                csr.E, nv.ptr(d), nv.stream())
+    return d
+
+
+def use_hip_grad(*tensors):
+    """sampling.grad_method == "hip" and every tensor is CUDA fp32: the one switch of every HIP backward (read here, at call
+    time: this module does not import sampling when it is loaded)."""
+    from . import sampling
+    return sampling._use_hip_grad(*tensors)
+
+
+def _slot_rows(csr):
+    """int64 [E]: the row of every slot (a search per slot: nothing waits for the host)"""
+    return torch.searchsorted(csr.rowptr, torch.arange(csr.E, device=csr.rowptr.device), right=True) - 1
+
+
+def spmm_torch(tcsr, x, val=None):
+    """spmm_csr as a differentiable torch expression over an [E, H] tensor (grad_method "torch", N != V, other dtypes)"""
+    msg = x[tcsr.col.long().to(x.device)]
+    if val is not None:
+        msg = msg * val.view(-1, 1)
+    return torch.zeros((tcsr.V, x.size(1)), dtype=msg.dtype, device=x.device).index_add_(0, _slot_rows(tcsr).to(x.device), msg)
+
+
+class SpmmFn(torch.autograd.Function):
+    """Differentiable ps_spmm_csr_exact over a TargetCSR: out[r] = sum over the slots e of row r of val[e] x[col[e]].
+    dx[s] = sum over the edges leaving s of val[e] g[target(e)]: the same kernel over the source-grouped CSR with g as the feature
+    matrix and val carried to that slot order; dval[e] = g[r] . x[col[e]]: ps_sddmm_csr, computed (and x saved for it) only when
+    val needs a gradient.  No float atomics and no [E, H] tensor in either direction: the same bits on every run."""
+
+    @staticmethod
+    def forward(ctx, tcsr, x, val):
+        ctx.tcsr = tcsr
+        ctx.save_for_backward(val, x if val is not None and ctx.needs_input_grad[2] else None)
+        return spmm_csr_exact(tcsr, x.contiguous(), None if val is None else val.contiguous())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        val, x = ctx.saved_tensors
+        tcsr = ctx.tcsr
+        need_x, need_val = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        # a backward that is itself recorded (create_graph) keeps the differentiable torch code
+        if not use_hip_grad(grad_out) or (torch.is_grad_enabled() and grad_out.requires_grad):
+            rows, cols = _slot_rows(tcsr), tcsr.col.long()
+            dx = dval = None
+            if need_x:
+                msg = grad_out[rows] if val is None else grad_out[rows] * val.view(-1, 1)
+                dx = torch.zeros_like(grad_out).index_add_(0, cols, msg)
+            if need_val:
+                dval = (grad_out[rows] * x[cols]).sum(dim=1)
+            return None, dx, dval
+        g = grad_out.contiguous()                                     # out.sum().backward() hands over a stride-0 tensor
+        dx = dval = None
+        if need_x:
+            scsr, index = tcsr.source()
+            dx = spmm_csr_exact(scsr, g, None if val is None else val[index])
+        if need_val:
+            dval = sddmm_csr(tcsr, x.contiguous(), g)
+        return None, dx, dval
+
+
+def spmm(tcsr, x, val=None):
+    """spmm_csr_exact that stays on the autograd tape when `x` or `val` needs a gradient.  The torch expression serves where the
+    kernels do not: sampling.grad_method == "torch", tensors that are not CUDA fp32, x with another row count than the graph."""
+    floats = (x,) if val is None else (x, val)
+    if not use_hip_grad(*floats) or int(x.size(0)) != tcsr.V:
+        return spmm_torch(tcsr, x, val)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in floats):
+        return SpmmFn.apply(tcsr, x, val)
+    return spmm_csr_exact(tcsr, x.contiguous(), None if val is None else val.contiguous())

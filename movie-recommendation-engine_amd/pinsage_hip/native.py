@@ -104,6 +104,10 @@ PROTOTYPES = {
     "ps_ivf_topk_workspace_bytes": "z qqiiiiq",
     "ps_ivf_topk": "i pqipiqppqpiipppzp",
     "ps_spmm_csr": "i ppppqiqqpp",
+    "ps_spmm_exact_slice": "i",
+    "ps_spmm_csr_exact_workspace_bytes": "z qi",
+    "ps_spmm_csr_exact": "i ppppqiqqppzp",
+    "ps_sddmm_csr": "i pppqpqiqpp",
     "ps_cooc_planes_bytes": "z qqi",
     "ps_cooc_planes": "i pppqqqipzppp",
     "ps_cooc_pairs": "i pqqiqpqpqppp",
