@@ -260,10 +260,10 @@ extern "C" int ps_cooc_planes(const int32_t *user, const int32_t *item, const in
     if (planes_bytes < need) return PS_EWORKSPACE;
     const Fmt f = fmt_of(max_mult);
     hipStream_t s = ps_stream(stream);
-    if (hipMemsetAsync(planes, 0, need, s) != hipSuccess) return PS_ELAUNCH;
-    if (hipMemsetAsync(item_stats, 0, (size_t)(2 * M) * sizeof(int64_t), s) != hipSuccess) return PS_ELAUNCH;
-    if (hipMemsetAsync(item_stats + 2 * M, 0x7f, (size_t)M * sizeof(int64_t), s) != hipSuccess) return PS_ELAUNCH;
-    if (hipMemsetAsync(max_seen, 0, sizeof(int32_t), s) != hipSuccess) return PS_ELAUNCH;
+    if (ps_fill_async(planes, 0, need, s) != hipSuccess) return PS_ELAUNCH;
+    if (ps_fill_async(item_stats, 0, (size_t)(2 * M) * sizeof(int64_t), s) != hipSuccess) return PS_ELAUNCH;
+    if (ps_fill_async(item_stats + 2 * M, 0x7f, (size_t)M * sizeof(int64_t), s) != hipSuccess) return PS_ELAUNCH;
+    if (ps_fill_async(max_seen, 0, sizeof(int32_t), s) != hipSuccess) return PS_ELAUNCH;
     if (n == 0) return PS_OK;
     int64_t grid = ps_cdiv(n, 256);
     if (grid > 256 * 64) grid = 256 * 64;
@@ -284,7 +284,7 @@ extern "C" int ps_cooc_pairs(const void *planes, int64_t U, int64_t M, int max_m
     if (!planes || !item_stats || !count || !h_count || (capacity > 0 && !records)) return PS_EINVAL;
     if (plane_tiles(M) / 2 > 65535) return PS_EUNSUPPORTED;             // one grid row per 64-item block row
     hipStream_t s = ps_stream(stream);
-    if (hipMemsetAsync(count, 0, sizeof(int64_t), s) != hipSuccess) return PS_ELAUNCH;
+    if (ps_fill_async(count, 0, sizeof(int64_t), s) != hipSuccess) return PS_ELAUNCH;
     int4 *rec = reinterpret_cast<int4 *>(records);
     unsigned long long *cnt = reinterpret_cast<unsigned long long *>(count);
     hipLaunchKernelGGL(cooc_self_kernel, dim3((unsigned)ps_cdiv(M, 256)), dim3(256), 0, s, item_stats, M, thr, rec, capacity, cnt);

@@ -275,8 +275,8 @@ extern "C" int ps_cooc_pairs_sparse(const int64_t *iptr, const int32_t *iuser, c
     hipStream_t s = ps_stream(stream);
     char *ws = reinterpret_cast<char *>(workspace);
     unsigned long long *counters = reinterpret_cast<unsigned long long *>(ws);
-    if (hipMemsetAsync(count, 0, sizeof(int64_t), s) != hipSuccess) return PS_ELAUNCH;
-    if (hipMemsetAsync(counters, 0, COUNTERS_BYTES, s) != hipSuccess) return PS_ELAUNCH;
+    if (ps_fill_async(count, 0, sizeof(int64_t), s) != hipSuccess) return PS_ELAUNCH;
+    if (ps_fill_async(counters, 0, COUNTERS_BYTES, s) != hipSuccess) return PS_ELAUNCH;
     int64_t per_cu = (int64_t)(160 * 1024) / (int64_t)lds;           // resident workgroups by LDS; 8 waves of 32 by threads
     per_cu = per_cu < 1 ? 1 : per_cu > 8 ? 8 : per_cu;
     int64_t grid = (int64_t)ncu * per_cu;

@@ -262,11 +262,18 @@ int radix_bits(int64_t V) {
 
 }  // namespace
 
+// The sort of ps_csr_build.  rocprim's default takes its onesweep path above 2^20 items, which clears its digit offsets and lookback
+// states with hipMemsetAsync: memset nodes when the call is captured, the kind whose ranges held other bytes from the second
+// replay on (csrc/ps_common.h: ps_fill_async).  With the merge-sort limit at the largest E the entry point takes, every edge list beyond one
+// block's 1024 items is sorted by rocprim's stable merge sort over the radix keys -- kernels only, the same result, whatever E.
+using CsrSortConfig = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config,
+                                                 ((size_t)1 << 32)>;
+
 extern "C" size_t ps_csr_build_workspace_bytes(int64_t E, int64_t V) {
     if (E <= 0) return ALIGN;
     size_t temp = 0;
     uint32_t *kn = nullptr;
-    (void)rocprim::radix_sort_pairs(nullptr, temp, kn, kn, kn, kn, (size_t)E, 0u, (unsigned)radix_bits(V), (hipStream_t)0);
+    (void)rocprim::radix_sort_pairs<CsrSortConfig>(nullptr, temp, kn, kn, kn, kn, (size_t)E, 0u, (unsigned)radix_bits(V), (hipStream_t)0);
     return 4 * ps_align256((size_t)E * sizeof(uint32_t)) + ps_align256(temp) + ALIGN;
 }
 
@@ -276,7 +283,7 @@ extern "C" int ps_csr_build(const int64_t *src, const int64_t *dst, const float 
     if (E < 0 || V < 0 || V >= ((int64_t)1 << 31) || E >= ((int64_t)1 << 32) || !rowptr) return PS_EINVAL;
     hipStream_t st = ps_stream(stream);
     if (E == 0) {
-        if (hipMemsetAsync(rowptr, 0, (size_t)(V + 1) * sizeof(int64_t), st) != hipSuccess) return PS_ELAUNCH;
+        if (ps_fill_async(rowptr, 0, (size_t)(V + 1) * sizeof(int64_t), st) != hipSuccess) return PS_ELAUNCH;
         return PS_OK;
     }
     if (!src || !dst || !col || !wsorted || !workspace) return PS_EINVAL;
@@ -291,14 +298,14 @@ extern "C" int ps_csr_build(const int64_t *src, const int64_t *dst, const float 
     size_t temp_bytes = workspace_bytes - (size_t)((base + 4 * seg) - reinterpret_cast<char *>(workspace));
     size_t need = 0;
     const unsigned bits = (unsigned)radix_bits(V);
-    if (rocprim::radix_sort_pairs(nullptr, need, keys_in, keys_out, vals_in, vals_out, (size_t)E, 0u, bits, st) != hipSuccess)
+    if (rocprim::radix_sort_pairs<CsrSortConfig>(nullptr, need, keys_in, keys_out, vals_in, vals_out, (size_t)E, 0u, bits, st) != hipSuccess)
         return PS_ELAUNCH;
     if (need > temp_bytes) return PS_EWORKSPACE;
     int64_t grid = ps_cdiv(E, 256);
     if (grid > 8192) grid = 8192;
     hipLaunchKernelGGL(prep_keys_kernel, dim3((unsigned)grid), dim3(256), 0, st, src, E, keys_in, vals_in);
     PS_CHECK_LAUNCH();
-    if (rocprim::radix_sort_pairs(temp, need, keys_in, keys_out, vals_in, vals_out, (size_t)E, 0u, bits, st) != hipSuccess)
+    if (rocprim::radix_sort_pairs<CsrSortConfig>(temp, need, keys_in, keys_out, vals_in, vals_out, (size_t)E, 0u, bits, st) != hipSuccess)
         return PS_ELAUNCH;
     hipLaunchKernelGGL(rowptr_kernel, dim3((unsigned)grid), dim3(256), 0, st, keys_out, E, V, rowptr);
     PS_CHECK_LAUNCH();

@@ -1225,6 +1225,12 @@ extern "C" int ps_lsh_expand(const uint8_t *codes, int64_t n, int cs, void *plan
     return launch_expand(reinterpret_cast<const uint32_t *>(codes), n, cs / 8, planes, ps_stream(stream));
 }
 
+// not part of the C ABI (tests): the slices the plan cuts the table into (two or more: slice_merge_kernel runs); 0 = shape not served
+extern "C" int ps_debug_hm_slices(int64_t nq, int64_t N, int cs, int k) {
+    const Plan p = make_plan(nq, N, cs, k);
+    return p.ok ? p.slices : 0;
+}
+
 extern "C" size_t ps_hamming_topk_mfma_workspace_bytes(int64_t nq, int64_t N, int cs, int k) {
     const Plan p = make_plan(nq, N, cs, k);
     return p.ok ? p.total : 0;                                // 0 = shape not served by the MFMA path

@@ -176,7 +176,7 @@ extern "C" int ps_hardest_negative(const float *Q, int64_t B, int D, const float
     if ((flags & PS_HN_PER_QUERY) && (flags & PS_HN_EXCLUDE_DIAG)) return PS_EINVAL;
     hipStream_t st = ps_stream(stream);
     unsigned long long *w = reinterpret_cast<unsigned long long *>(best);
-    if (hipMemsetAsync(w, 0, sizeof(unsigned long long) * (size_t)B, st) != hipSuccess) return PS_ELAUNCH;
+    if (ps_fill_async(w, 0, sizeof(unsigned long long) * (size_t)B, st) != hipSuccess) return PS_ELAUNCH;
     if (flags & PS_HN_PER_QUERY) {
         hipLaunchKernelGGL(hardest_rows_kernel, dim3(grid_for(B * N, 256)), dim3(256), 0, st, Q, X, B, N, D, w);
         PS_CHECK_LAUNCH();

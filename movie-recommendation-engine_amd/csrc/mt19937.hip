@@ -743,7 +743,7 @@ static int mt_generate(const uint32_t *state_in, int pos_in, int64_t skip, int64
     if (n > 0 && !out && !raw_out) return PS_EINVAL;
     hipStream_t st = ps_stream(stream);
     if (n == 0 && skip == 0) {                          // nothing consumed: state unchanged
-        if (hipMemcpyAsync(state_out, state_in, MT_N * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return PS_ELAUNCH;
+        if (ps_copy_async(state_out, state_in, MT_N * 4, st) != hipSuccess) return PS_ELAUNCH;
         hipLaunchKernelGGL(mt_set_pos_kernel, dim3(1), dim3(1), 0, st, pos_in, pos_out);
         PS_CHECK_LAUNCH();
         return PS_OK;
@@ -867,7 +867,7 @@ static int mt_generate(const uint32_t *state_in, int pos_in, int64_t skip, int64
         PS_CHECK_LAUNCH();
     } else {
         // 1. W1 (part 0 of tmpA, the other parts zero) and word 0
-        if (hipMemsetAsync(tmpA, 0, WSZ * 4, st) != hipSuccess) return PS_ELAUNCH;
+        if (ps_fill_async(tmpA, 0, WSZ * 4, st) != hipSuccess) return PS_ELAUNCH;
         hipLaunchKernelGGL(mt_prepare_kernel, dim3(1), dim3(256), 0, st, state_in, pos_in, tmpA, word0);
         PS_CHECK_LAUNCH();
         // 2. base jump to chunk c0: offset c0 * CHUNK words = set bits of c0 at levels CHUNK_LOG2 + b
@@ -880,7 +880,7 @@ static int mt_generate(const uint32_t *state_in, int pos_in, int64_t skip, int64
             PS_CHECK_LAUNCH();
             uint32_t *t = cur; cur = nxt; nxt = t;
         }
-        if (hipMemcpyAsync(states, cur, WSZ * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return PS_ELAUNCH;
+        if (ps_copy_async(states, cur, WSZ * 4, st) != hipSuccess) return PS_ELAUNCH;
         if (one_round) {                                // after a skipped prefix: window c0 is in `states`, JP parts
             hipLaunchKernelGGL(mt_fold_kernel, dim3(3), dim3(256), 0, st, states, plainS);
             PS_CHECK_LAUNCH();
@@ -1008,7 +1008,7 @@ static int mt_generate(const uint32_t *state_in, int pos_in, int64_t skip, int64
         hipLaunchKernelGGL(mt_final_state_kernel, dim3(1), dim3(640), 0, st, raw, p.w_lo, p.key_w, p.pos_out, state_out, pos_out);
         PS_CHECK_LAUNCH();
     } else {
-        if (hipMemcpyAsync(state_out, state_in, MT_N * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return PS_ELAUNCH;
+        if (ps_copy_async(state_out, state_in, MT_N * 4, st) != hipSuccess) return PS_ELAUNCH;
         hipLaunchKernelGGL(mt_set_pos_kernel, dim3(1), dim3(1), 0, st, p.pos_out, pos_out);
         PS_CHECK_LAUNCH();
     }

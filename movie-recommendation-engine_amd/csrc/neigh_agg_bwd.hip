@@ -573,7 +573,7 @@ extern "C" int ps_gather_bwd(const int64_t *rptr, const int32_t *slots, int64_t 
     if (!gx) return PS_EINVAL;
     hipStream_t st = ps_stream(stream);
     if (B == 0) {                                             // nothing points at any row: every element is +0.0
-        if (hipMemsetAsync(gx, 0, (size_t)N * H * sizeof(float), st) != hipSuccess) return PS_ELAUNCH;
+        if (ps_fill_async(gx, 0, (size_t)N * H * sizeof(float), st) != hipSuccess) return PS_ELAUNCH;
         return PS_OK;
     }
     if (!rptr || !slots || !g || (coef != nullptr) == (arg != nullptr) || !workspace) return PS_EINVAL;
@@ -636,7 +636,7 @@ extern "C" int ps_attention_bwd_cols(const int64_t *rptr, const int32_t *slots, 
     if (!dv) return PS_EINVAL;
     hipStream_t st = ps_stream(stream);
     if (B == 0) {
-        if (hipMemsetAsync(dv, 0, (size_t)N * Hd * sizeof(float), st) != hipSuccess) return PS_ELAUNCH;
+        if (ps_fill_async(dv, 0, (size_t)N * Hd * sizeof(float), st) != hipSuccess) return PS_ELAUNCH;
         return PS_OK;
     }
     if (!rptr || !slots || !ds || !u || !v || !w2 || !workspace) return PS_EINVAL;

@@ -214,8 +214,8 @@ extern "C" int ps_ppr_push(const int64_t *in_rowptr, const int32_t *in_src, cons
     char *base = ps_ws_base(workspace);
     double *c[2] = {reinterpret_cast<double *>(base), reinterpret_cast<double *>(base + cbytes)};
     uint8_t *act[2] = {reinterpret_cast<uint8_t *>(base + 2 * cbytes), reinterpret_cast<uint8_t *>(base + 2 * cbytes + abytes)};
-    if (hipMemsetAsync(base, 0, 2 * cbytes + 2 * abytes, st) != hipSuccess) return PS_ELAUNCH;
-    if (hipMemsetAsync(score, 0, (size_t)Vp * Sc * sizeof(double), st) != hipSuccess) return PS_ELAUNCH;
+    if (ps_fill_async(base, 0, 2 * cbytes + 2 * abytes, st) != hipSuccess) return PS_ELAUNCH;
+    if (ps_fill_async(score, 0, (size_t)Vp * Sc * sizeof(double), st) != hipSuccess) return PS_ELAUNCH;
     hipLaunchKernelGGL(seed_kernel, dim3((unsigned)ps_cdiv(S, 256)), dim3(256), 0, st, sources, S, Sc, Vp, score);
     PS_CHECK_LAUNCH();
     PushArgs a;

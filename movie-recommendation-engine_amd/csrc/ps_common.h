@@ -39,6 +39,61 @@ static inline int64_t ps_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t ps_align256(size_t x) { return (x + 255) / 256 * 256; }
 static inline char *ps_ws_base(void *workspace) { return reinterpret_cast<char *>(ps_align256(reinterpret_cast<size_t>(workspace))); }
 
+// Fills and device-to-device copies inside an entry point are plain kernels (ps_fill_async / ps_copy_async), not
+// hipMemsetAsync / hipMemcpyAsync.  Captured into a hipGraph those two become memset / memcpy NODES.  Observed on the MI355X
+// (tests/test_hip_abi_contract.py against a build with hipMemsetAsync; capture by torch.cuda.graph, one stream): the first
+// replay was right, and from the second replay on the ranges that seven entry points clear held bytes that were neither the
+// zeros asked for nor what the range held before -- pointer-like words in ps_graph_stats' flags.  What the node wrote was not
+// isolated outside that setting, so this is a record of the symptom, not a statement about the runtime.  A kernel node replays
+// like every other launch of the call.  (Only memset nodes were seen to fail; the generator's three copies go the same way so
+// that a captured call consists of kernel nodes alone.  rocprim's sort: see csrc/csr_build.hip.)  Any alignment and size; nothing
+// outside [dst, dst + nbytes) is written.
+static __global__ void ps_fill_kernel(unsigned char *dst, unsigned int byte, size_t nbytes) {
+    size_t head = (16 - (reinterpret_cast<size_t>(dst) & 15)) & 15;          // bytes in front of the first 16-byte boundary
+    if (head > nbytes) head = nbytes;
+    const size_t body = (nbytes - head) / 16;
+    const unsigned int w = (byte & 0xffu) * 0x01010101u;
+    const uint4 v = make_uint4(w, w, w, w);
+    uint4 *b = reinterpret_cast<uint4 *>(dst + head);
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < body; i += stride) b[i] = v;
+    if (blockIdx.x == 0) {                                                   // fewer than 16 bytes at either end
+        for (size_t i = threadIdx.x; i < head; i += blockDim.x) dst[i] = (unsigned char)byte;
+        for (size_t i = head + body * 16 + threadIdx.x; i < nbytes; i += blockDim.x) dst[i] = (unsigned char)byte;
+    }
+}
+static __global__ void ps_copy_kernel(unsigned char *dst, const unsigned char *src, size_t nbytes) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (((reinterpret_cast<size_t>(dst) | reinterpret_cast<size_t>(src)) & 15) == 0) {
+        const size_t body = nbytes / 16;
+        const uint4 *s = reinterpret_cast<const uint4 *>(src);
+        uint4 *d = reinterpret_cast<uint4 *>(dst);
+        for (size_t i = tid; i < body; i += stride) d[i] = s[i];
+        for (size_t i = body * 16 + tid; i < nbytes; i += stride) dst[i] = src[i];
+    } else {
+        for (size_t i = tid; i < nbytes; i += stride) dst[i] = src[i];
+    }
+}
+static inline unsigned ps_fill_grid(size_t nbytes) {
+    const size_t g = (nbytes / 16 + 255) / 256;
+    return (unsigned)(g < 1 ? 1 : g > 4096 ? 4096 : g);
+}
+// hipMemsetAsync(dst, byte, nbytes, st) as a kernel; hipSuccess for nbytes == 0
+static inline hipError_t ps_fill_async(void *dst, int byte, size_t nbytes, hipStream_t st) {
+    if (nbytes == 0) return hipSuccess;
+    hipLaunchKernelGGL(ps_fill_kernel, dim3(ps_fill_grid(nbytes)), dim3(256), 0, st, reinterpret_cast<unsigned char *>(dst),
+                       (unsigned int)byte, nbytes);
+    return hipGetLastError();
+}
+// hipMemcpyAsync(dst, src, nbytes, hipMemcpyDeviceToDevice, st) as a kernel (the ranges must not overlap)
+static inline hipError_t ps_copy_async(void *dst, const void *src, size_t nbytes, hipStream_t st) {
+    if (nbytes == 0) return hipSuccess;
+    hipLaunchKernelGGL(ps_copy_kernel, dim3(ps_fill_grid(nbytes)), dim3(256), 0, st, reinterpret_cast<unsigned char *>(dst),
+                       reinterpret_cast<const unsigned char *>(src), nbytes);
+    return hipGetLastError();
+}
+
 // internal (not part of the C ABI): grouped x W^T of csrc/dense_mfma.hip, used by the inverted-file scan
 int psi_linear_grouped(const float *x, int64_t M, int K, const float *W, int ldw, float *y, const int64_t *grp, int max_cols,
                        ps_stream_t stream);

@@ -92,7 +92,7 @@ extern "C" int ps_spmm_csr(const int64_t *rowptr, const int32_t *col, const floa
     if (V == 0) return PS_OK;
     if (!out) return PS_EINVAL;
     hipStream_t st = ps_stream(stream);
-    if (hipMemsetAsync(out, 0, (size_t)V * H * sizeof(float), st) != hipSuccess) return PS_ELAUNCH;
+    if (ps_fill_async(out, 0, (size_t)V * H * sizeof(float), st) != hipSuccess) return PS_ELAUNCH;
     if (E == 0) return PS_OK;
     if (!rowptr || !col || !x) return PS_EINVAL;
     const int64_t waves = ps_cdiv(E, SLICE);

@@ -258,7 +258,7 @@ extern "C" int ps_spmm_csr_exact(const int64_t *rowptr, const int32_t *col, cons
     if (!out) return PS_EINVAL;
     hipStream_t st = ps_stream(stream);
     if (E == 0) {                                             // every row is empty: +0.0 everywhere
-        if (hipMemsetAsync(out, 0, (size_t)V * H * sizeof(float), st) != hipSuccess) return PS_ELAUNCH;
+        if (ps_fill_async(out, 0, (size_t)V * H * sizeof(float), st) != hipSuccess) return PS_ELAUNCH;
         return PS_OK;
     }
     if (!rowptr || !col || !x || !workspace) return PS_EINVAL;
@@ -267,7 +267,7 @@ extern "C" int ps_spmm_csr_exact(const int64_t *rowptr, const int32_t *col, cons
     const int64_t grid = ps_cdiv(waves, 4);
     if (waves > 0x7fffffff) return PS_EUNSUPPORTED;           // a wave's number is an int
     // the empty rows (no wave visits them) are the zeros of this fill; every other row is stored once by one of the launches
-    if (hipMemsetAsync(out, 0, (size_t)V * H * sizeof(float), st) != hipSuccess) return PS_ELAUNCH;
+    if (ps_fill_async(out, 0, (size_t)V * H * sizeof(float), st) != hipSuccess) return PS_ELAUNCH;
     float *part = reinterpret_cast<float *>(ps_ws_base(workspace));
     const bool vec4 = (H % 4 == 0) && aligned16({x, out});
     if (vec4) {

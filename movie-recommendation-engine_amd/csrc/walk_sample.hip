@@ -861,7 +861,7 @@ extern "C" int ps_graph_stats(const int64_t *rowptr, const int32_t *col, int64_t
                               ps_stream_t stream) {
     if (!rowptr || !flags || (E > 0 && !col)) return PS_EINVAL;
     hipStream_t st = ps_stream(stream);
-    if (hipMemsetAsync(flags, 0, 2 * sizeof(int64_t), st) != hipSuccess) return PS_ELAUNCH;
+    if (ps_fill_async(flags, 0, 2 * sizeof(int64_t), st) != hipSuccess) return PS_ELAUNCH;
     int64_t n = E > V ? E : V;
     int64_t grid = ps_cdiv(n > 0 ? n : 1, 256);
     if (grid > 4096) grid = 4096;

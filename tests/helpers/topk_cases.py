@@ -249,9 +249,8 @@ def assert_exact(c):
         assert qm * qm + xm * xm + 2 * qm * xm < EXACT, c.name     # |q|^2, |x|^2, their sum, 2 q.x and the difference
 
 
-@functools.lru_cache(maxsize=None)
-def _oracle(name):
-    c = cases()[name]
+def oracle_of(c):
+    """the oracle of any Case object, in the table or not (computed on every call)"""
     vals = np.full((c.nq, c.k), -np.inf if c.kind == "dot" else FLT_MAX, dtype=np.float32)
     ids = np.full((c.nq, c.k), -1, dtype=np.int64)
     for r in range(c.nq):
@@ -262,6 +261,11 @@ def _oracle(name):
     vals.setflags(write=False)
     ids.setflags(write=False)
     return vals, ids
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle(name):
+    return oracle_of(cases()[name])
 
 
 def oracle(c):
