@@ -348,6 +348,40 @@ int ps_permute_k(const float *W, int64_t rows, int K, int ld, float *out, ps_str
 int ps_linear(const float *x, int64_t M, int K, const float *W, int ldw, const float *b, int N,
               const float *x2, int K2, const float *W2, int ldw2, int flags, float *y, ps_stream_t stream);
 
+/* ---- the same layers under loss.backward() (model/pinsage.py:202,235-240,248-249 on the tape; train.py:72-82), csrc/linear_bwd.hip:
+ * the weight and bias gradients of y = epilogue(x W^T + b) and the backward of the epilogue.  (The input gradient g W is ps_linear
+ * over W^T, a chain over n ascending.)  Caller-allocated buffers, no allocation, no synchronisation, no float atomics: every output
+ * bit is a function of the inputs, whatever the workspace held before the call.
+ *
+ * ps_linear_wgrad: g float[M,N] (the gradient of the pre-activation), x float[M,K], both dense -> dW float[N,K] (dense) and, unless
+ *   db is NULL, db float[N].
+ *   Partitions.  The rows are cut into partitions of P = ps_linear_wgrad_partition(M) consecutive rows: P = 512, doubled while
+ *   ceil(M / P) > 256 -- a function of M alone (not of N, K, the device, the environment or the alignment of the operands).
+ *   s_p[n,k] is the chain acc = fmaf(g[m,n], x[m,k], acc) over the rows m of partition p ascending, from +0.0.
+ *   dW[n,k] = ((s_0 + s_1) + s_2) + ... in partition order; s_0 alone when M <= P.  db[n] is the same form with x = 1: the chain
+ *   acc = acc + g[m,n].  M == 0 gives zeros, whatever g and x are.
+ *   workspace: ps_linear_wgrad_workspace_bytes(M, N, K) bytes (0 for M <= P: then the workspace may be NULL), any alignment, not
+ *   preserved between calls.  One launch for M <= P; otherwise two: the partitions' tiles into the workspace with plain stores,
+ *   then the sums.  Any N, K >= 1 and any 4-byte alignment; 16-byte aligned g and x with N % 4 == 0 and K % 4 == 0 are read with
+ *   16-byte requests and give the same bits.
+ *   PS_EINVAL for M < 0, N < 1, K < 1, a null dW, (M > 0) a null g or x, (M > P) a null workspace; PS_EWORKSPACE for a short one.
+ *
+ * ps_linear_epilogue_bwd: t float[M,N] = the layer's activation after bias and ReLU and before the row norm, g float[M,N] = the
+ *   gradient of the layer's output -> gz float[M,N] = the gradient of the pre-activation, one wave per row.  gz may be g.
+ *   flags: a subset of PS_RELU | PS_L2NORM, any other bit PS_EINVAL.
+ *   PS_L2NORM: nrm and c = max(nrm, 1e-12f) from t exactly as ps_bn_apply makes them (per-lane fmaf chain over the lane's columns
+ *   64 VEC k + VEC lane + e ascending, VEC = 4 when N % 4 == 0 and t, g, gz are 16-byte aligned, else 1; the wave sum; sqrtf);
+ *   y_c = t_c / c; s = sum_c g_c y_c as lane chains part = fmaf(g_c, y_c, part) from +0.0 and the same wave sum;
+ *   gt_c = fmaf(-y_c, s, g_c) / c where nrm >= 1e-12f or nrm is NaN, gt_c = g_c / c below the clamp (F.normalize's clamp_min, whose
+ *   gradient is zero there).  Without PS_L2NORM gt = g.
+ *   PS_RELU: gz_c = t_c > 0 ? gt_c : +0.0f.  Without it gz = gt.
+ *   PS_OK for M == 0, whatever the pointers; PS_EINVAL for M < 0, N < 1, (M > 0) a null g or gz, or a null t with a flag set. */
+int64_t ps_linear_wgrad_partition(int64_t M);
+size_t ps_linear_wgrad_workspace_bytes(int64_t M, int N, int K);
+int ps_linear_wgrad(const float *g, int64_t M, int N, const float *x, int K, float *dW, float *db, void *workspace,
+                    size_t workspace_bytes, ps_stream_t stream);
+int ps_linear_epilogue_bwd(const float *t, const float *g, int64_t M, int N, int flags, float *gz, ps_stream_t stream);
+
 /* One layer of the pooled branch in one call: y = epilogue( x W^T + pool(h_full) W2^T + b ), where pool(h_full) is
  * ps_importance_pool(h_full, n_full, H, ids, counts, wts, nvalid, M, T, max_idx, renorm) and the rest is ps_linear with
  * x2 = that pooled matrix (K2 = H): the same bits as that pair.  Rows that keep no neighbour skip the K2 half (their pooled row is

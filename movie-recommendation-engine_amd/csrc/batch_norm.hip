@@ -13,29 +13,13 @@
 //                    registers between the sum of squares and the division; longer rows are read a second time (by the lane
 //                    that writes the same addresses afterwards, so y may be z).
 #include "ps_common.h"
+#include "row_norm.h"
 
 namespace {
 
 constexpr int BN_ROWS = 128;       // rows per partition of the statistics pass
 constexpr int BN_UNROLL = 8;       // rows a wave has in flight
 constexpr int KEEP = 4;            // sweeps of a row that ps_bn_apply keeps in registers
-
-template <int VEC>
-__device__ __forceinline__ void load_vec(const float *__restrict__ p, bool ok, float (&r)[VEC]) {
-    if (VEC == 4) {
-        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (ok) q = *reinterpret_cast<const float4 *>(p);
-        r[0] = q.x; r[1 % VEC] = q.y; r[2 % VEC] = q.z; r[3 % VEC] = q.w;
-    } else {
-        r[0] = ok ? p[0] : 0.f;
-    }
-}
-
-template <int VEC>
-__device__ __forceinline__ void store_vec(float *__restrict__ p, const float (&r)[VEC]) {
-    if (VEC == 4) *reinterpret_cast<float4 *>(p) = make_float4(r[0], r[1 % VEC], r[2 % VEC], r[3 % VEC]);
-    else p[0] = r[0];
-}
 
 // part[p, 0, c] = sum of z[r, c], part[p, 1, c] = sum of z[r, c]^2 over the rows r of partition p (double[P, 2, N])
 template <int VEC>
@@ -179,8 +163,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float *z, int64_t M
         }
         float nrm = 1.f;
         if (l2) {
-            nrm = sqrtf(ps_wave_sum_f32(acc));
-            nrm = nrm < 1e-12f ? 1e-12f : nrm;                           // a NaN norm stays (fmaxf would drop it): the whole row is NaN
+            nrm = ps_row_clamp(ps_row_norm(acc));                        // a NaN norm stays: the whole row is NaN
         }
 #pragma unroll
         for (int k = 0; k < KEEP; ++k) {

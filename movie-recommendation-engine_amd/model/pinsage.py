@@ -9,12 +9,17 @@ implements `aggr='add'` message passing itself.
 What runs where
   pooled branch (model/pinsage.py:217-240,248-249)   -> ps_importance_pool + ps_linear (fp32 MFMA,
         bias/ReLU/concat/L2-normalise fused); with autograd enabled the same kernel does the
-        pooling forward and torch does the (differentiable) dense layers.
-  MLP branch (:205-214, what train.py uses)           -> plain torch nn.Linear (autograd), as in the reference.
+        pooling forward and the dense layers are differentiable (last entry).
+  MLP branch (:205-214, what train.py uses)           -> nn.Linear as in the reference; under autograd on the GPU, last entry.
   edge_index branch (:243-245, GraphConv)             -> ps_spmm_csr over the edges grouped by target node (no grad); under
         autograd ps_spmm_csr_exact forward, the same kernel over the source-grouped edges and ps_sddmm_csr backward
         (pinsage_hip.graph.spmm: no float atomics, no [E, H] tensor); sampling.grad_method = "torch" and CPU tensors keep
         torch's x[src] / index_add_.
+  dense layers under autograd, all three branches     -> dense.linear on the tape (pinsage_hip.dense.LinearFn: ps_linear forward
+        with the fused bias / ReLU and ps_bn_apply's row norm; ps_linear_epilogue_bwd, ps_linear_wgrad and ps_linear backward;
+        lin_update takes its two operands without a cat) for CUDA fp32 under sampling.grad_method = "hip", branch by branch as
+        HIP_LINEAR says (DESIGN.md §4 "Dense layers, training": a branch whose step measured slower than torch's keeps nn.Linear).
+        grad_method = "torch", CPU tensors and other dtypes keep the torch layers.
 """
 from __future__ import annotations
 
@@ -32,6 +37,25 @@ from pinsage_hip.shard import HipOps, fused_self_update
 
 _OPS = HipOps()
 _TCSR_CACHE = {}
+# which branches take dense.linear for their layers under autograd (decided by measurement: DESIGN.md §4)
+HIP_LINEAR = {"mlp": True, "edge": True, "pooled": True}
+
+
+def _hip_linear(branch, module, x):
+    """the dense layers of `branch` go through dense.linear on the tape: the branch's switch is on, the input and the parameters
+    are CUDA fp32, sampling.grad_method is "hip" """
+    return HIP_LINEAR[branch] and graph_mod.use_hip_grad(x, *module.parameters())
+
+
+def _lin(layer, x, relu=False, l2norm=False):
+    return dense.linear(x, layer.weight, layer.bias, relu=relu, l2norm=l2norm)
+
+
+def _lin_update(layer, x_self, x_neigh):
+    """normalize(relu(layer(cat([x_self, x_neigh])))) without the cat: the column halves of the weight are views of the leaf, and
+    autograd carries their dense gradients back into it"""
+    H = x_self.size(1)
+    return dense.linear(x_self, layer.weight[:, :H], layer.bias, x2=x_neigh, W2=layer.weight[:, H:], relu=True, l2norm=True)
 
 
 def _target_csr(edge_index, num_nodes):
@@ -57,6 +81,11 @@ class GraphConv(nn.Module):
         self.lin_update = nn.Linear(2 * out_channels, out_channels)
 
     def forward(self, x, edge_index=None, edge_weight=None, importance_weights=None):
+        if edge_index is not None and torch.is_grad_enabled() and _hip_linear("edge", self, x) \
+                and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            x_neigh = self.propagate(edge_index, x=_lin(self.lin_neigh, x), edge_weight=edge_weight,
+                                     importance_weights=importance_weights)
+            return _lin_update(self.lin_update, _lin(self.lin_self, x), x_neigh)
         x_self = self.lin_self(x)
         if edge_index is None:
             x_neigh = torch.zeros_like(x_self)
@@ -220,13 +249,23 @@ class PinSage(nn.Module):
             edge_index, sampled_neighbors, importance_weights = None, edge_index, sampled_neighbors
 
         if edge_index is None and (sampled_neighbors is None or importance_weights is None):
-            # MLP branch (:205-214): plain torch, differentiable -- what train.py trains
+            # MLP branch (:205-214), what train.py trains: dense.linear on the tape, or plain torch
+            if self._needs_grad(x) and _hip_linear("mlp", self, x):
+                h = _lin(self.input_proj, x, relu=True)
+                for i in range(self.num_layers):
+                    h = _lin(self.convs[i].lin_self, h, relu=True)
+                return _lin(self.output_proj, h, l2norm=True)
             h = F.relu(self.input_proj(x))
             for i in range(self.num_layers):
                 h = F.relu(self.convs[i].lin_self(h))
             return F.normalize(self.output_proj(h), p=2, dim=1)
 
         if edge_index is not None:
+            if self._needs_grad(x) and _hip_linear("edge", self, x):
+                h = _lin(self.input_proj, x, relu=True)
+                for i in range(self.num_layers):
+                    h = self.convs[i](h, edge_index)
+                return _lin(self.output_proj, h, l2norm=True)
             h = F.relu(self.input_proj(x))
             for i in range(self.num_layers):
                 h = self.convs[i](h, edge_index)
@@ -234,6 +273,13 @@ class PinSage(nn.Module):
 
         # ---- importance-pooled branch (:217-240, :248-249) ----
         if self._needs_grad(x):
+            if _hip_linear("pooled", self, x):
+                h = _lin(self.input_proj, x, relu=True)
+                for i in range(self.num_layers):
+                    nb, wt = self._layer_inputs(sampled_neighbors, importance_weights, i)
+                    h_neigh = self.importance_pooling(h, nb, wt)
+                    h = _lin_update(self.convs[i].lin_update, _lin(self.convs[i].lin_self, h), h_neigh)
+                return _lin(self.output_proj, h, l2norm=True)
             h = F.relu(self.input_proj(x))
             for i in range(self.num_layers):
                 nb, wt = self._layer_inputs(sampled_neighbors, importance_weights, i)

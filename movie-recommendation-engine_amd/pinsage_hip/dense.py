@@ -5,6 +5,8 @@ from __future__ import annotations
 import os
 
 import torch
+import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import native as nv
 
@@ -97,7 +99,33 @@ def stage_lsh(A):
 def linear(x, W, b=None, x2=None, W2=None, relu=False, l2norm=False):
     """y = epi(x @ W.T (+ x2 @ W2.T) + b): nn.Linear / F.relu / torch.cat / F.normalize of
     PinSage.forward (reference model/pinsage.py:202,235-240,248-249) in one kernel.  W / W2: matrices or StagedWeights (both
-    or neither)."""
+    or neither).
+    With autograd on and an operand that requires a gradient the call stays on the tape: LinearFn (the same kernel forward,
+    ps_linear_epilogue_bwd / ps_linear_wgrad / ps_linear backward) for CUDA fp32 operands under sampling.grad_method == "hip",
+    linear_torch elsewhere ("torch", other dtypes, CPU tensors; a backward that is itself to be differentiated needs "torch" too:
+    LinearFn is once-differentiable).  StagedWeights are derived copies, not leaves: ValueError there."""
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (x, W, b, x2, W2)):
+        if isinstance(W, StagedWeight) or isinstance(W2, StagedWeight):
+            raise ValueError("a StagedWeight is a derived copy, not a leaf: pass the weight itself where a gradient is needed")
+        from .graph import use_hip_grad
+        if use_hip_grad(*(t for t in (x, W, b, x2, W2) if t is not None)):
+            return LinearFn.apply(x, W, b, x2, W2, bool(relu), bool(l2norm))
+        return linear_torch(x, W, b, x2, W2, relu, l2norm)
+    return _linear_fwd(x, W, b, x2, W2, relu, l2norm)
+
+
+def linear_torch(x, W, b=None, x2=None, W2=None, relu=False, l2norm=False):
+    """linear() as a differentiable torch expression (grad_method "torch", other dtypes)"""
+    y = F.linear(x, W, b)
+    if x2 is not None:
+        y = y + F.linear(x2, W2)
+    if relu:
+        y = F.relu(y)
+    return F.normalize(y, p=2, dim=1) if l2norm else y
+
+
+def _linear_fwd(x, W, b=None, x2=None, W2=None, relu=False, l2norm=False):
+    """ps_linear, off the tape"""
     staged = isinstance(W, StagedWeight)
     if x2 is not None and isinstance(W2, StagedWeight) != staged:
         raise ValueError("W and W2 must both be staged or both plain")
@@ -127,6 +155,90 @@ def linear(x, W, b=None, x2=None, W2=None, relu=False, l2norm=False):
         nv.call("ps_linear", nv.ptr(x), M, K, nv.ptr(Wk, contiguous=False), ldw, nv.ptr(b), N, nv.ptr(x2), K2,
                 nv.ptr(W2k, contiguous=False), ldw2, flags, nv.ptr(y), nv.stream())
     return y
+
+
+def linear_wgrad(g, x, bias=True):
+    """(dW [N, K], db [N] or None) = (g.T @ x, g.sum(0)) of g [M, N], x [M, K] (ps_linear_wgrad): per element the fmaf chain over
+    the rows of a partition of ps_linear_wgrad_partition(M) rows, the partitions added in order -- no atomics, the same bits on
+    every run.  The workspace comes from torch's allocator."""
+    _require_cuda(g, x)
+    if g.dtype != torch.float32 or x.dtype != torch.float32:
+        raise TypeError("fp32 expected")
+    if g.dim() != 2 or x.dim() != 2 or g.size(0) != x.size(0):
+        raise ValueError(f"shape mismatch: g {tuple(g.shape)} vs x {tuple(x.shape)}")
+    g, x = g.contiguous(), x.contiguous()
+    M, N, K = g.size(0), g.size(1), x.size(1)
+    dW = torch.empty((N, K), dtype=torch.float32, device=g.device)
+    db = torch.empty(N, dtype=torch.float32, device=g.device) if bias else None
+    ws, wsb = nv.workspace("ps_linear_wgrad_workspace_bytes", g.device, M, N, K)
+    with torch.cuda.device(g.device):
+        nv.call("ps_linear_wgrad", nv.ptr(g), M, N, nv.ptr(x), K, nv.ptr(dW), nv.ptr(db), nv.ptr(ws), wsb, nv.stream())
+    return dW, db
+
+
+def linear_epilogue_bwd(t, g, relu, l2norm, out=None):
+    """The gradient of the pre-activation from the gradient g of linear()'s output and the saved activation t (after bias and
+    ReLU, before the norm): ps_linear_epilogue_bwd, one wave per row.  out=g works in place."""
+    _require_cuda(t, g, out)
+    if t.dtype != torch.float32 or g.dtype != torch.float32:
+        raise TypeError("fp32 expected")
+    if t.dim() != 2 or t.shape != g.shape:
+        raise ValueError(f"shape mismatch: t {tuple(t.shape)} vs g {tuple(g.shape)}")
+    t = t.contiguous()
+    if out is None:
+        g = g.contiguous()
+        out = torch.empty_like(g)
+    elif out.dtype != torch.float32 or out.shape != g.shape or not out.is_contiguous() or not g.is_contiguous() or out.device != g.device:
+        raise ValueError("out must be a contiguous fp32 tensor of g's shape on its device (and g contiguous)")
+    flags = (nv.PS_RELU if relu else 0) | (nv.PS_L2NORM if l2norm else 0)
+    with torch.cuda.device(g.device):
+        nv.call("ps_linear_epilogue_bwd", nv.ptr(t), nv.ptr(g), t.size(0), t.size(1), flags, nv.ptr(out), nv.stream())
+    return out
+
+
+class LinearFn(torch.autograd.Function):
+    """Differentiable linear() for CUDA fp32 operands.  Forward: t = ps_linear with the bias and the ReLU and without the norm --
+    the inference call's bits -- and, with l2norm, y = ps_bn_apply(t, mean 0, scale 1, beta 0, PS_L2NORM), the row norm the
+    backward restates (fmaf(t - 0, 1, +0) is t).  Backward: gz = ps_linear_epilogue_bwd(t, gy); dW, db = ps_linear_wgrad(gz, x);
+    dW2 = ps_linear_wgrad(gz, x2); dx = ps_linear(gz, W^T) and dx2 likewise, each only for an input that needs it.  t is kept only
+    when the ReLU or the norm needs it, x / x2 only when a weight needs a gradient, W / W2 only when an input does.  No float
+    atomics, nothing waits for the host: the same bits on every run."""
+
+    @staticmethod
+    def forward(ctx, x, W, b, x2, W2, relu, l2norm):
+        need = ctx.needs_input_grad
+        t = _linear_fwd(x, W, b, x2, W2, relu, False)
+        y = t
+        if l2norm:
+            N = t.size(1)
+            zero, one = torch.zeros(N, dtype=torch.float32, device=t.device), torch.ones(N, dtype=torch.float32, device=t.device)
+            y = batch_norm_apply(t, zero, one, zero, False, True)
+        ctx.relu, ctx.l2norm = relu, l2norm
+        ctx.save_for_backward(x if need[1] else None, W if need[0] else None,
+                              x2 if x2 is not None and need[4] else None, W2 if x2 is not None and need[3] else None,
+                              t if relu or l2norm else None)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, W, x2, W2, t = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        g = gy.contiguous()                                           # y.sum().backward() hands over a stride-0 tensor
+        gz = linear_epilogue_bwd(t, g, ctx.relu, ctx.l2norm) if t is not None else g
+        dx = dW = db = dx2 = dW2 = None
+        if need[1]:
+            dW, db = linear_wgrad(gz, x, bias=need[2])
+        elif need[2]:
+            # the bias gradient alone: the weight gradient against a column of ones is the same chain, acc = fmaf(g, 1, acc)
+            db = linear_wgrad(gz, torch.ones((gz.size(0), 1), dtype=torch.float32, device=gz.device), bias=False)[0].view(-1)
+        if need[4]:
+            dW2 = linear_wgrad(gz, x2, bias=False)[0]
+        if need[0]:
+            dx = _linear_fwd(gz, W.t().contiguous())
+        if need[3]:
+            dx2 = _linear_fwd(gz, W2.t().contiguous())
+        return dx, dW, db, dx2, dW2, None, None
 
 
 BN_STATS_ROWS = 128       # rows per partition of ps_bn_batch_stats' fixed summation order (csrc/batch_norm.hip)

@@ -78,6 +78,10 @@ PROTOTYPES = {
     "ps_bn_apply": "i pqipppipp",
     "ps_permute_k": "i pqiipp",
     "ps_linear": "i pqipipipipiipp",
+    "ps_linear_wgrad_partition": "q q",
+    "ps_linear_wgrad_workspace_bytes": "z qii",
+    "ps_linear_wgrad": "i pqipipppzp",
+    "ps_linear_epilogue_bwd": "i ppqiipp",
     "ps_gcn_layer_workspace_bytes": "z qi",
     "ps_gcn_layer": "i pqipipipqippppiqipiippzp",
     "ps_gcn_order": "i ppiqiqppp",
