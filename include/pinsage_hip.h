@@ -382,6 +382,41 @@ int ps_linear_wgrad(const float *g, int64_t M, int N, const float *x, int K, flo
                     size_t workspace_bytes, ps_stream_t stream);
 int ps_linear_epilogue_bwd(const float *t, const float *g, int64_t M, int N, int flags, float *gz, ps_stream_t stream);
 
+/* ---- GraphConvLayer under loss.backward() (model/layers.py on the tape): the backward of training-mode batch norm with the layer's
+ * epilogue, csrc/batch_norm_bwd.hip.  Caller-allocated buffers, no allocation, no synchronisation, no float atomics: every output
+ * bit is a function of the inputs, whatever the workspace held before the call.
+ *
+ * ps_bn_bwd: the backward of y = epilogue(fmaf(z - mean, scale, beta)) (ps_bn_apply) where mean, var, scale float[N] are
+ *   ps_bn_batch_stats' outputs for this same z float[M,N]: training-mode nn.BatchNorm1d, so the dependence of the statistics on z is
+ *   part of the gradient.  gy float[M,N] is the gradient of y.  Outputs, each may be NULL (not wanted): gz float[M,N] the gradient
+ *   of z, dgamma float[N], dbeta float[N] the gradients of the batch norm's weight and bias.  Nothing but z and the column vectors
+ *   is read: t below is recomputed with ps_bn_apply's bits.  flags: a subset of PS_RELU | PS_L2NORM, as ps_bn_apply.
+ *   Per column, fp32:   rstd = 1.0f / sqrtf(var + eps)  (sqrt and division correctly rounded).
+ *   Per element, fp32:  d = z - mean (rounded); a = fmaf(d, scale, beta); t = PS_RELU ? (a < 0 ? +0 : a) : a; xh = d * rstd.
+ *   Per row, PS_L2NORM only, ps_linear_epilogue_bwd's values for (t, gy): the lane chains acc = fmaf(t, t, acc) over the columns
+ *     64 VEC k + VEC lane + e ascending, the wave sum, nrm = sqrtf(sum), c = max(nrm, 1e-12f); s = the wave sum of the lane chains
+ *     acc = fmaf(gy, t / c, acc).  VEC = 4 when N % 4 == 0 and z, gy, gz (if given), mean, var, scale, beta are 16-byte aligned,
+ *     else 1 (ps_bn_apply's rule).
+ *   ga = ps_linear_epilogue_bwd's output for (t, gy, flags): nrm < 1e-12f ? gy / c : fmaf(-(t / c), s, gy) / c with PS_L2NORM, gy
+ *     without; +0.0f where PS_RELU and not t > 0.
+ *   Per column, fp64:   S1 = sum_r (double)ga, S2 = sum_r (double)ga * (double)xh (the product of two fp32 values is exact), in
+ *     ps_bn_batch_stats' summation order: partitions of 128 consecutive rows, within a partition four strided row subsets
+ *     (r0 + w, r0 + w + 4, ...) summed sequentially and added as ((s0 + s1) + s2) + s3, the partitions added ascending from 0.0.
+ *   dbeta = (float)S1, dgamma = (float)S2; k1 = dbeta / (float)M, k2 = dgamma / (float)M in fp32;
+ *   gz = scale * fmaf(-xh, k2, ga - k1)  (the difference rounded, then the fmaf, then the product).
+ *   gz may be gy: a lane reads gy[c] for the last time before it writes gz[c].
+ *   Four launches (three without PS_L2NORM, one fewer when gz is NULL): the rows' (nrm, s), the partitions' column sums, their sum
+ *   with dbeta / dgamma / k1 / k2, and gz.  z and gy are read again by each; no [M, N] intermediate exists.
+ *   workspace: ps_bn_bwd_workspace_bytes(M, N) bytes (0 for M < 2 or N < 1), 8-byte aligned, not preserved between calls.
+ *   PS_EINVAL for M < 2, N < 1, a flag bit other than the two, a null z, gy, mean, var, scale, beta or workspace, a workspace that is
+ *   not 8-byte aligned; PS_EWORKSPACE for a short one; PS_EUNSUPPORTED for M > 2^33 - 4 or more than 65 535 column
+ *   blocks (N > 65 535 * 64 VEC).  Nothing is written in any of these cases.
+ *   PS_OK and nothing written when all three outputs are NULL. */
+size_t ps_bn_bwd_workspace_bytes(int64_t M, int N);
+int ps_bn_bwd(const float *z, const float *gy, int64_t M, int N, const float *mean, const float *var, const float *scale,
+              const float *beta, float eps, int flags, float *gz, float *dgamma, float *dbeta, void *workspace,
+              size_t workspace_bytes, ps_stream_t stream);
+
 /* One layer of the pooled branch in one call: y = epilogue( x W^T + pool(h_full) W2^T + b ), where pool(h_full) is
  * ps_importance_pool(h_full, n_full, H, ids, counts, wts, nvalid, M, T, max_idx, renorm) and the rest is ps_linear with
  * x2 = that pooled matrix (K2 = H): the same bits as that pair.  Rows that keep no neighbour skip the K2 half (their pooled row is

@@ -17,7 +17,7 @@
 
 namespace {
 
-constexpr int BN_ROWS = 128;       // rows per partition of the statistics pass
+constexpr int BN_ROWS = PS_BN_ROWS; // rows per partition of the statistics pass
 constexpr int BN_UNROLL = 8;       // rows a wave has in flight
 constexpr int KEEP = 4;            // sweeps of a row that ps_bn_apply keeps in registers
 
@@ -108,10 +108,7 @@ template <int VEC>
 __device__ __forceinline__ void bn_affine(const float (&zz)[VEC], const float (&mm)[VEC], const float (&sc)[VEC],
                                           const float (&bb)[VEC], bool relu, float (&t)[VEC]) {
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-        const float a = fmaf(zz[e] - mm[e], sc[e], bb[e]);
-        t[e] = (relu && a < 0.f) ? 0.f : a;
-    }
+    for (int e = 0; e < VEC; ++e) t[e] = ps_bn_act(zz[e] - mm[e], sc[e], bb[e], relu);
 }
 
 template <int VEC>

@@ -220,11 +220,7 @@ __global__ __launch_bounds__(256) void epilogue_bwd_kernel(const float *t, const
             load_vec<VEC>(tr + col, true, tt);
             load_vec<VEC>(gr + col, true, gg);
 #pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                float gt = gg[e];
-                if (l2) gt = below ? gg[e] / c : fmaf(-(tt[e] / c), s, gg[e]) / c;
-                o[e] = (relu && !(tt[e] > 0.f)) ? 0.f : gt;
-            }
+            for (int e = 0; e < VEC; ++e) o[e] = ps_epilogue_ga(tt[e], gg[e], relu, l2, c, below, s);
             store_vec<VEC>(zr + col, o);
         }
     }

@@ -8,7 +8,12 @@ ps_bn_batch_stats (column mean / biased variance from fp64 sums, running statist
 layer is one ps_linear launch with its ReLU + L2 epilogue.  The three pooling layers pad their python lists once on the host
 (with the reference's filtering and weight quirks, see _pad) and run on ps_importance_pool / ps_gather_max.  CPU tensors, other
 dtypes, calls that autograd has to see and a batch norm that is not the default configuration run the torch code
-(`_forward_torch`)."""
+(`_forward_torch`).
+
+Training on the kernels is a switch: `GraphConvLayer.grad_method = "hip"` (class or instance; the default is "torch") together with
+sampling.grad_method == "hip" keeps a training-mode call with gradients on the tape as a differentiable dense.linear over the
+composed weights and dense.batch_norm, whose backward is ps_bn_bwd (`_forward_hip_tape`: same output and buffer bits as off the
+tape).  Eval mode with gradients (M >= 2), an empty batch and a non-default batch norm run `_forward_torch` under either setting."""
 from __future__ import annotations
 
 import numpy as np
@@ -49,14 +54,29 @@ class GraphConvLayer(nn.Module):
         nn.init.zeros_(self.linear_neigh.bias)
         nn.init.zeros_(self.linear_out.bias)
 
+    # how a call that autograd has to see is computed: "torch" (the default) runs `_forward_torch`; "hip" -- together with
+    # sampling.grad_method == "hip" -- keeps the kernels on the tape (`_forward_hip_tape`).  Set on the class or on an instance.
+    grad_method = "torch"
+
     def forward(self, x, neigh_x):
-        if self._hip_serves(x, neigh_x):
-            return self._forward_hip(x, neigh_x)
+        if self.grad_method not in ("hip", "torch"):
+            raise ValueError(f"GraphConvLayer.grad_method must be 'hip' or 'torch', not {self.grad_method!r}")
+        if self._hip_shapes(x, neigh_x):
+            if _off_tape(self, x, neigh_x):
+                return self._forward_hip(x, neigh_x)
+            M = x.size(0)
+            if self.grad_method == "hip" and sampling.grad_method == "hip" and (M == 1 or (M >= 2 and self.bn.training)):
+                return self._forward_hip_tape(x, neigh_x)
         return self._forward_torch(x, neigh_x)
 
     def _hip_serves(self, x, neigh_x):
+        """do the kernels serve the call off the tape?"""
+        return self._hip_shapes(x, neigh_x) and _off_tape(self, x, neigh_x)
+
+    def _hip_shapes(self, x, neigh_x):
+        """the shape / dtype / device / batch-norm-configuration conditions of the kernels, on or off the tape"""
         bn = self.bn
-        if not (_cuda_fp32(x) and _cuda_fp32(neigh_x) and x.dim() == 2 and neigh_x.dim() == 2 and _off_tape(self, x, neigh_x)):
+        if not (_cuda_fp32(x) and _cuda_fp32(neigh_x) and x.dim() == 2 and neigh_x.dim() == 2):
             return False
         if x.size(0) != neigh_x.size(0) or x.size(1) != self.linear_self.in_features \
                 or neigh_x.size(1) != self.linear_neigh.in_features or x.device != neigh_x.device:
@@ -66,25 +86,27 @@ class GraphConvLayer(nn.Module):
         return all(t.device == x.device and t.dtype == torch.float32 for t in list(self.parameters()) + list(self.buffers())
                    if t is not bn.num_batches_tracked)
 
-    def _composed(self, s=None, shift=None):
+    def _composed(self, s=None, shift=None, tape=False):
         """(W1, W2, b) with linear_out(cat[linear_self(x), linear_neigh(n)]) = x W1^T + n W2^T + b: W1 = Wo[:, :O] Ws,
         W2 = Wo[:, O:] Wn, b = Wo[:, :O] bs + Wo[:, O:] bn + bo (three small GEMMs on the weights instead of two [M, O]
-        intermediates).  With s / shift (fp32 [O]) the per-column affine map t -> s t + shift is folded in: the rows of Wo are
-        scaled before the products and b becomes Wo'[:, :O] bs + Wo'[:, O:] bn + (s bo + shift).  The two halves of Wo are made
-        contiguous (and scaled) in one launch.  Nothing is cached: see shard.fused_self_update."""
-        Ws, bs = self.linear_self.weight.detach(), self.linear_self.bias.detach()
-        Wn, bn_ = self.linear_neigh.weight.detach(), self.linear_neigh.bias.detach()
-        Wo, bo = self.linear_out.weight.detach(), self.linear_out.bias.detach()
+        intermediates).  With s / shift (fp32 [O]; off the tape only) the per-column affine map t -> s t + shift is folded in: the
+        rows of Wo are scaled before the products and b becomes Wo'[:, :O] bs + Wo'[:, O:] bn + (s bo + shift).  The two halves
+        of Wo are made contiguous (and scaled) in one launch.  Nothing is cached: see shard.fused_self_update.
+        tape=True: over the six leaves themselves, so that the three dense.linear calls and the copy of Wo's halves stay on the
+        autograd tape and carry dW1, dW2, db back to them -- the same calls, hence the same bits."""
+        params = (self.linear_self.weight, self.linear_self.bias, self.linear_neigh.weight, self.linear_neigh.bias,
+                  self.linear_out.weight, self.linear_out.bias)
+        Ws, bs, Wn, bn_, Wo, bo = params if tape else (p.detach() for p in params)
         O = Ws.size(0)
         halves = Wo.view(O, 2, O).permute(1, 0, 2)                        # [2, O, O]: Wo[:, :O], Wo[:, O:]
-        Wo12 = torch.empty((2, O, O), dtype=Wo.dtype, device=Wo.device)
         if s is None:
-            Wo12.copy_(halves)
+            Wo12 = halves.contiguous()
         else:
+            Wo12 = torch.empty((2, O, O), dtype=Wo.dtype, device=Wo.device)
             torch.mul(halves, s[None, :, None], out=Wo12)
             bo = torch.addcmul(shift, s, bo)
-        W1 = dense.linear(Wo12[0], Ws.t().contiguous())
-        W2 = dense.linear(Wo12[1], Wn.t().contiguous())
+        W1 = dense.linear(Wo12[0], Ws.t())                                # dense.linear makes the transposed weight contiguous
+        W2 = dense.linear(Wo12[1], Wn.t())
         b = dense.linear(bs.reshape(1, -1), Wo12[0], bo, x2=bn_.reshape(1, -1), W2=Wo12[1]).reshape(-1)
         return W1, W2, b
 
@@ -109,9 +131,25 @@ class GraphConvLayer(nn.Module):
             bn.num_batches_tracked.add_(1)
             return dense.batch_norm_apply(z, mean, scale, beta, relu=True, l2norm=True, out=z)
 
+    def _forward_hip_tape(self, x, neigh_x):
+        """grad_method "hip", a call autograd has to see: training mode with M >= 2 -- one differentiable dense.linear over
+        [x | neigh_x] with the composed weights, then dense.batch_norm (ps_bn_batch_stats + ps_bn_apply forward, ps_bn_bwd
+        backward; z is the only [M, O] tensor saved) -- and M == 1 in either mode (no batch norm, the buffers untouched).  The
+        output and the buffers have the bits of `_forward_hip`.  Eval mode with M >= 2, M == 0 and a non-default batch norm stay
+        with `_forward_torch`."""
+        bn = self.bn
+        W1, W2, b = self._composed(tape=True)
+        if x.size(0) == 1:
+            return dense.linear(x, W1, b, x2=neigh_x, W2=W2, relu=True, l2norm=True)
+        z = dense.linear(x, W1, b, x2=neigh_x, W2=W2)
+        y = dense.batch_norm(z, bn.weight, bn.bias, bn.eps, bn.momentum, bn.running_mean, bn.running_var, relu=True, l2norm=True)
+        with torch.no_grad():
+            bn.num_batches_tracked.add_(1)
+        return y
+
     def _forward_torch(self, x, neigh_x):
-        """the reference's forward in torch (CPU tensors, other dtypes, training with gradients, a non-default bn); the
-        concatenation is replaced by the two column halves of linear_out"""
+        """the reference's forward in torch (CPU tensors, other dtypes, calls on the tape unless grad_method is "hip", a
+        non-default bn); the concatenation is replaced by the two column halves of linear_out"""
         O = self.linear_self.out_features
         Wo = self.linear_out.weight
         out = F.linear(self.linear_self(x), Wo[:, :O]) + F.linear(self.linear_neigh(neigh_x), Wo[:, O:], self.linear_out.bias)

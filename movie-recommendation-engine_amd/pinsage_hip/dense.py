@@ -303,7 +303,94 @@ def batch_norm_apply(z, mean, scale, beta, relu, l2norm, out=None):
     return out
 
 
-GCN_MIN_ROWS, GCN_MAX_T = 64 * 384, 16      # the M / T gates of ps_gcn_layer: gcn_orders makes no order the layer call would refuse
+def batch_norm_bwd(z, gy, mean, var, scale, beta, eps, relu, l2norm, need_gz=True, need_affine=True, out=None):
+    """(gz [M, N], dgamma [N], dbeta [N]) of y = epi((z - mean) * scale + beta) where mean / var / scale are batch_norm_stats' of
+    this same z, M >= 2 (ps_bn_bwd): the backward of training-mode nn.BatchNorm1d with the layer's epilogue, the statistics'
+    dependence on z included.  t is recomputed from z with the forward's bits; the workspace comes from torch's allocator.
+    need_gz / need_affine False: that output is None and not computed.  out: a contiguous fp32 [M, N] device tensor for gz;
+    out=gy works in place."""
+    _require_cuda(z, gy, mean, var, scale, beta, out)
+    if z.dtype != torch.float32 or gy.dtype != torch.float32:
+        raise TypeError("fp32 expected")
+    if z.dim() != 2 or z.shape != gy.shape:
+        raise ValueError(f"shape mismatch: z {tuple(z.shape)} vs gy {tuple(gy.shape)}")
+    z = z.contiguous()
+    M, N = z.size(0), z.size(1)
+    if M < 2:
+        raise ValueError("batch norm needs at least two rows")
+    mean, var, scale, beta = (_fp32_vec(n, t, N, z.device) for n, t in (("mean", mean), ("var", var), ("scale", scale), ("beta", beta)))
+    gz = dgamma = dbeta = None
+    if out is None:
+        gy = gy.contiguous()
+        if need_gz:
+            gz = torch.empty((M, N), dtype=torch.float32, device=z.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (M, N) or not out.is_contiguous() or not gy.is_contiguous() \
+            or out.device != z.device:
+        raise ValueError("out must be a contiguous fp32 [M, N] tensor on the device of z (and gy contiguous)")
+    elif need_gz:
+        gz = out
+    if need_affine:
+        dgamma, dbeta = (torch.empty(N, dtype=torch.float32, device=z.device) for _ in range(2))
+    flags = (nv.PS_RELU if relu else 0) | (nv.PS_L2NORM if l2norm else 0)
+    ws, wsb = nv.workspace("ps_bn_bwd_workspace_bytes", z.device, M, N)
+    with torch.cuda.device(z.device):
+        nv.call("ps_bn_bwd", nv.ptr(z), nv.ptr(gy), M, N, nv.ptr(mean), nv.ptr(var), nv.ptr(scale), nv.ptr(beta), float(eps), flags,
+                nv.ptr(gz), nv.ptr(dgamma), nv.ptr(dbeta), nv.ptr(ws), wsb, nv.stream())
+    return gz, dgamma, dbeta
+
+
+def batch_norm_torch(z, gamma, beta, eps=1e-5, momentum=0.1, running_mean=None, running_var=None, relu=False, l2norm=False):
+    """batch_norm() as a differentiable torch expression (grad_method "torch", other dtypes, CPU tensors)"""
+    y = F.batch_norm(z, running_mean, running_var, gamma, beta, training=True, momentum=momentum, eps=eps)
+    if relu:
+        y = F.relu(y)
+    return F.normalize(y, p=2, dim=1) if l2norm else y
+
+
+def batch_norm(z, gamma, beta, eps=1e-5, momentum=0.1, running_mean=None, running_var=None, relu=False, l2norm=False):
+    """Training-mode batch norm of z [M >= 2, N] with GraphConvLayer's epilogue: y = epi((z - mean) * gamma / sqrt(var + eps) +
+    beta) over the batch statistics of z; running_mean / running_var (both or neither) are updated in place, once.
+    Off the tape: batch_norm_stats + batch_norm_apply into a new tensor.  With autograd on and z, gamma or beta requiring a
+    gradient the call stays on the tape: BatchNormFn (the same two kernels forward, ps_bn_bwd backward) for CUDA fp32 operands under
+    sampling.grad_method == "hip", batch_norm_torch elsewhere ("torch", other dtypes, CPU tensors; a backward that is itself to be
+    differentiated needs "torch" too: BatchNormFn is once-differentiable)."""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (z, gamma, beta)):
+        from .graph import use_hip_grad
+        if use_hip_grad(*(t for t in (z, gamma, beta, running_mean, running_var) if t is not None)):
+            with torch.no_grad():
+                mean, var, scale = batch_norm_stats(z, gamma, eps, momentum, running_mean, running_var)
+            return BatchNormFn.apply(z, gamma, beta, mean, var, scale, float(eps), bool(relu), bool(l2norm))
+        return batch_norm_torch(z, gamma, beta, eps, momentum, running_mean, running_var, relu, l2norm)
+    mean, _, scale = batch_norm_stats(z, gamma, eps, momentum, running_mean, running_var)
+    return batch_norm_apply(z, mean, scale, beta, relu, l2norm)
+
+
+class BatchNormFn(torch.autograd.Function):
+    """Differentiable batch_norm() for CUDA fp32 operands.  The statistics (mean, var, scale = gamma / sqrt(var + eps)) are made
+    before `apply`, off the tape, and enter as non-differentiable vectors: the backward accounts for their dependence on z (and
+    of scale on gamma) analytically, as ps_bn_bwd defines it.  Forward: ps_bn_apply, the inference call's bits.  Saved: z and the
+    column vectors; neither t nor y.  Backward: one ps_bn_bwd -- gz only if z needs it, dgamma / dbeta only if gamma or beta does.
+    No float atomics, nothing waits for the host: the same bits on every run."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, mean, var, scale, eps, relu, l2norm):
+        ctx.eps, ctx.relu, ctx.l2norm = eps, relu, l2norm
+        z = z.contiguous()
+        ctx.save_for_backward(z, mean, var, scale, beta)
+        return batch_norm_apply(z, mean, scale, beta, relu, l2norm)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        z, mean, var, scale, beta = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gy = gy.contiguous()                                          # y.sum().backward() hands over a stride-0 tensor
+        gz, dgamma, dbeta = batch_norm_bwd(z, gy, mean, var, scale, beta, ctx.eps, ctx.relu, ctx.l2norm, need_gz=need[0],
+                                           need_affine=need[1] or need[2])
+        return gz, dgamma if need[1] else None, dbeta if need[2] else None, None, None, None, None, None, None
+
+
+GCN_MIN_ROWS, GCN_MAX_T = 64 * 384, 16     # the M / T gates of ps_gcn_layer: gcn_orders makes no order the layer call would refuse
 
 
 def gcn_orders(ids, nvalid, max_idx):

@@ -76,6 +76,8 @@ PROTOTYPES = {
     "ps_bn_stats_workspace_bytes": "z qi",
     "ps_bn_batch_stats": "i pqipffppppppzp",
     "ps_bn_apply": "i pqipppipp",
+    "ps_bn_bwd_workspace_bytes": "z qi",
+    "ps_bn_bwd": "i ppqippppfippppzp",
     "ps_permute_k": "i pqiipp",
     "ps_linear": "i pqipipipipiipp",
     "ps_linear_wgrad_partition": "q q",
