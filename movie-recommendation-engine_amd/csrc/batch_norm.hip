@@ -1,23 +1,20 @@
 // batch_norm.hip -- nn.BatchNorm1d of GraphConvLayer (reference model/layers.py:68-75) on gfx950: column statistics of z[M, N]
 // and the per-column affine map with the layer's ReLU and F.normalize behind it (two HBM-bound sweeps over z).
 //
-// ps_bn_batch_stats  one pass over z.  The rows are cut into partitions of BN_ROWS consecutive rows (a function of M only); a
-//                    workgroup takes one partition and 64 * VEC columns, its four waves take the partition's rows r0 + w,
-//                    r0 + w + 4, ... and every lane adds its columns' z and z * z in fp64 (the square of an fp32 value is exact
-//                    there).  The four waves' sums are added in wave order through LDS and written to the workspace; a second
-//                    kernel adds the partitions in ascending order, one lane per column, and makes mean / var / scale and the
-//                    running update.  No atomics, every workspace word that is read was written by this call: equal inputs give
-//                    equal bits.
-// ps_bn_apply        one wave per row, as importance_pool_kernel / gather_max_kernel: 16 B per lane when N % 4 == 0 and the
+// ps_bn_batch_stats  one pass over z, the column-sum skeleton of col_sums.h with z and z * z as the two addends (the square of an
+//                    fp32 value is exact in fp64): a workgroup takes a partition of PS_BN_ROWS rows and 64 * VEC columns and
+//                    strides over the partitions when there are more than 65 535; a second kernel adds the partitions in
+//                    ascending order, one lane per column, and makes mean / var / scale and the running update.
+// ps_bn_apply        one wave per row, the sweeps of row_sweep.h: 16 B per lane when N % 4 == 0 and the
 //                    pointers allow it, a scalar sweep otherwise, grid-stride over the rows.  Rows of up to KEEP sweeps stay in
 //                    registers between the sum of squares and the division; longer rows are read a second time (by the lane
 //                    that writes the same addresses afterwards, so y may be z).
 #include "ps_common.h"
-#include "row_norm.h"
+#include "col_sums.h"
+#include "row_sweep.h"
 
 namespace {
 
-constexpr int BN_ROWS = PS_BN_ROWS; // rows per partition of the statistics pass
 constexpr int BN_UNROLL = 8;       // rows a wave has in flight
 constexpr int KEEP = 4;            // sweeps of a row that ps_bn_apply keeps in registers
 
@@ -25,55 +22,22 @@ constexpr int KEEP = 4;            // sweeps of a row that ps_bn_apply keeps in 
 template <int VEC>
 __global__ __launch_bounds__(256) void bn_partial_kernel(const float *__restrict__ z, int64_t M, int N, int64_t P,
                                                          double *__restrict__ part) {
-    __shared__ double sh[3][2][64 * VEC];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int col = (int)blockIdx.y * 64 * VEC + lane * VEC;
-    const bool cact = col < N;
+    struct Row { float z[VEC]; };
+    const int col = (int)blockIdx.y * 64 * VEC + (threadIdx.x & 63) * VEC;
     for (int64_t p = blockIdx.x; p < P; p += gridDim.x) {
-        const int64_t r0 = p * BN_ROWS;
-        const int64_t r1 = (r0 + BN_ROWS < M) ? r0 + BN_ROWS : M;
-        double s[VEC], q[VEC];
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) { s[e] = 0.0; q[e] = 0.0; }
-        for (int64_t r = r0 + wave; r < r1; r += 4 * BN_UNROLL) {
-            float v[BN_UNROLL][VEC];
-#pragma unroll
-            for (int t = 0; t < BN_UNROLL; ++t) {
-                const int64_t rr = r + 4 * t;
-                load_vec<VEC>(z + rr * N + col, cact && rr < r1, v[t]);
-            }
-#pragma unroll
-            for (int t = 0; t < BN_UNROLL; ++t)                          // a row past the partition adds +0.0 twice: no change
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) {
-                    const double d = (double)v[t][e];
-                    s[e] += d;
-                    q[e] += d * d;
-                }
-        }
-        if (wave > 0) {
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                sh[wave - 1][0][lane * VEC + e] = s[e];
-                sh[wave - 1][1][lane * VEC + e] = q[e];
-            }
-        }
-        __syncthreads();
-        if (wave == 0 && cact) {
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                double ss = s[e], qq = q[e];
-#pragma unroll
-                for (int w = 0; w < 3; ++w) {
-                    ss += sh[w][0][lane * VEC + e];
-                    qq += sh[w][1][lane * VEC + e];
-                }
-                part[(p * 2 + 0) * N + col + e] = ss;
-                part[(p * 2 + 1) * N + col + e] = qq;
-            }
-        }
-        __syncthreads();                                                 // sh is reused by the next partition
+        ps_col_sums_partition<VEC, BN_UNROLL, false>(
+            M, N, p, col,
+            [&](int64_t rr, bool live) {
+                Row row;
+                load_vec<VEC>(z + rr * N + col, col < N && live, row.z);
+                return row;
+            },
+            [](const Row &row, int e, double &a, double &b) {
+                a = (double)row.z[e];                                    // a row past the partition: +0.0 and +0.0
+                b = a * a;
+            },
+            part);
+        __syncthreads();                                                 // the LDS words are reused by the next partition
     }
 }
 
@@ -83,14 +47,9 @@ __global__ __launch_bounds__(64) void bn_finish_kernel(const double *__restrict_
                                                        float *__restrict__ mean, float *__restrict__ var,
                                                        float *__restrict__ scale) {
     for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < N; c += gridDim.x * blockDim.x) {
-        double S = 0.0, Q = 0.0;
-#pragma unroll 32                                                        // the loads of 32 partitions in flight ahead of the two add chains
-        for (int64_t p = 0; p < P; ++p) {
-            S += part[(p * 2 + 0) * N + c];
-            Q += part[(p * 2 + 1) * N + c];
-        }
-        const double m = S / (double)M;
-        double v = Q / (double)M - m * m;
+        const double2 sq = ps_col_sums_finish(part, P, N, c);
+        const double m = sq.x / (double)M;
+        double v = sq.y / (double)M - m * m;
         v = v > 0.0 ? v : 0.0;
         mean[c] = (float)m;
         var[c] = (float)v;
@@ -144,19 +103,20 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float *z, int64_t M
 #pragma unroll
             for (int e = 0; e < VEC; ++e) acc = fmaf(t[k][e], t[k][e], acc);
         }
-        if (!fits && l2) {
+        // the rest of a long row, for both passes: use(col, cact, tt) gets the activation of every further sweep
+        auto rest = [&](auto use) {
             for (int c0 = KEEP * chunk; c0 < N; c0 += chunk) {
                 const int col = c0 + lane * VEC;
-                const bool cact = col < N;
-                float zz[VEC], mm[VEC], sc[VEC], bb[VEC], tt[VEC];
-                load_vec<VEC>(zr + col, cact, zz);
-                load_vec<VEC>(mean + col, cact, mm);
-                load_vec<VEC>(scale + col, cact, sc);
-                load_vec<VEC>(beta + col, cact, bb);
-                bn_affine<VEC>(zz, mm, sc, bb, relu, tt);
+                float tt[VEC];
+                ps_bn_act_vec<VEC>(zr, mean, scale, beta, col, col < N, relu, tt);
+                use(col, col < N, tt);
+            }
+        };
+        if (!fits && l2) {
+            rest([&](int, bool, const float (&tt)[VEC]) {
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) acc = fmaf(tt[e], tt[e], acc);
-            }
+            });
         }
         float nrm = 1.f;
         if (l2) {
@@ -173,38 +133,24 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float *z, int64_t M
             }
         }
         if (!fits) {
-            // the rest of a long row: every lane reads again what it is about to overwrite (y may be z)
-            for (int c0 = KEEP * chunk; c0 < N; c0 += chunk) {
-                const int col = c0 + lane * VEC;
-                const bool cact = col < N;
-                float zz[VEC], mm[VEC], sc[VEC], bb[VEC], tt[VEC];
-                load_vec<VEC>(zr + col, cact, zz);
-                load_vec<VEC>(mean + col, cact, mm);
-                load_vec<VEC>(scale + col, cact, sc);
-                load_vec<VEC>(beta + col, cact, bb);
-                bn_affine<VEC>(zz, mm, sc, bb, relu, tt);
+            // every lane reads again what it is about to overwrite (y may be z)
+            rest([&](int col, bool cact, const float (&tt)[VEC]) {
                 if (cact) {
+                    float o[VEC];
 #pragma unroll
-                    for (int e = 0; e < VEC; ++e) tt[e] = l2 ? tt[e] / nrm : tt[e];
-                    store_vec<VEC>(yr + col, tt);
+                    for (int e = 0; e < VEC; ++e) o[e] = l2 ? tt[e] / nrm : tt[e];
+                    store_vec<VEC>(yr + col, o);
                 }
-            }
+            });
         }
     }
-}
-
-inline int64_t bn_partitions(int64_t M) { return ps_cdiv(M, BN_ROWS); }
-
-inline unsigned row_grid(int64_t B) {          // 4 waves (rows) per workgroup; beyond 16 384 waves the rows are strided over
-    int64_t grid = ps_cdiv(B, 4);
-    return (unsigned)(grid > 256 * 16 ? 256 * 16 : grid);
 }
 
 }  // namespace
 
 extern "C" size_t ps_bn_stats_workspace_bytes(int64_t M, int N) {
     if (M < 2 || N < 1) return 0;
-    return (size_t)bn_partitions(M) * 2 * (size_t)N * sizeof(double);
+    return (size_t)ps_bn_partitions(M) * 2 * (size_t)N * sizeof(double);
 }
 
 extern "C" int ps_bn_batch_stats(const float *z, int64_t M, int N, const float *gamma, float eps, float momentum,
@@ -214,14 +160,11 @@ extern "C" int ps_bn_batch_stats(const float *z, int64_t M, int N, const float *
     if ((running_mean == nullptr) != (running_var == nullptr)) return PS_EINVAL;
     if (workspace_bytes < ps_bn_stats_workspace_bytes(M, N) || reinterpret_cast<size_t>(workspace) % 8 != 0) return PS_EINVAL;
     hipStream_t st = ps_stream(stream);
-    const int64_t P = bn_partitions(M);
+    const int64_t P = ps_bn_partitions(M);
     double *part = static_cast<double *>(workspace);
     const unsigned gx = (unsigned)(P > 65535 ? 65535 : P);
-    const bool vec4 = (N % 4 == 0) && (reinterpret_cast<size_t>(z) % 16 == 0);
-    if (vec4)
-        hipLaunchKernelGGL(bn_partial_kernel<4>, dim3(gx, (unsigned)ps_cdiv(N, 256)), dim3(256), 0, st, z, M, N, P, part);
-    else
-        hipLaunchKernelGGL(bn_partial_kernel<1>, dim3(gx, (unsigned)ps_cdiv(N, 64)), dim3(256), 0, st, z, M, N, P, part);
+    const bool vec4 = (N % 4 == 0) && ps_aligned16({z});
+    PS_LAUNCH_VEC(bn_partial_kernel<VEC>, vec4, dim3(gx, (unsigned)ps_cdiv(N, 64 * VEC)), dim3(256), st, z, M, N, P, part);
     PS_CHECK_LAUNCH();
     hipLaunchKernelGGL(bn_finish_kernel, dim3((unsigned)ps_cdiv(N, 64)), dim3(64), 0, st, part, P, M, N, gamma, (double)eps,
                        (double)momentum, running_mean, running_var, mean, var, scale);
@@ -235,12 +178,8 @@ extern "C" int ps_bn_apply(const float *z, int64_t M, int N, const float *mean, 
     if (M == 0) return PS_OK;                                 // before the pointers: an empty tensor's base is NULL
     if (!z || !mean || !scale || !beta || !y) return PS_EINVAL;
     hipStream_t st = ps_stream(stream);
-    const bool vec4 = (N % 4 == 0) && ((reinterpret_cast<size_t>(z) | reinterpret_cast<size_t>(y) | reinterpret_cast<size_t>(mean) |
-                                        reinterpret_cast<size_t>(scale) | reinterpret_cast<size_t>(beta)) % 16 == 0);
-    if (vec4)
-        hipLaunchKernelGGL(bn_apply_kernel<4>, dim3(row_grid(M)), dim3(256), 0, st, z, M, N, mean, scale, beta, flags, y);
-    else
-        hipLaunchKernelGGL(bn_apply_kernel<1>, dim3(row_grid(M)), dim3(256), 0, st, z, M, N, mean, scale, beta, flags, y);
+    const bool vec4 = (N % 4 == 0) && ps_aligned16({z, y, mean, scale, beta});
+    PS_LAUNCH_VEC(bn_apply_kernel<VEC>, vec4, dim3(ps_row_grid(M)), dim3(256), st, z, M, N, mean, scale, beta, flags, y);
     PS_CHECK_LAUNCH();
     return PS_OK;
 }

@@ -6,12 +6,11 @@
 // the host: equal inputs give equal bits.  The operation order is stated in include/pinsage_hip.h.
 //
 // Four passes, any N:
-//   bn_bwd_rowscal_kernel   PS_L2NORM only.  One wave per row, the sweeps of epilogue_bwd_kernel: the lane chains of t^2, the norm,
-//                           s = sum gy (t / c); (nrm, s) go to the workspace, 2 floats per row.
-//   bn_bwd_partial_kernel   shaped like bn_partial_kernel: a workgroup takes one partition of PS_BN_ROWS rows and 64 * VEC columns,
-//                           its waves the rows r0 + w, r0 + w + 4, ...; every lane recomputes ga (ps_epilogue_ga) and xh per element
-//                           and adds ga and ga * xh in fp64 (the product of two fp32 values is exact there).  The waves are added in
-//                           wave order through LDS: part[P, 2, N].
+//   bn_bwd_rowscal_kernel   PS_L2NORM only.  One wave per row, ps_row_norm_sums (row_sweep.h, the code of epilogue_bwd_kernel) over
+//                           the recomputed t: (nrm, s) go to the workspace, 2 floats per row.
+//   bn_bwd_partial_kernel   the column-sum skeleton of col_sums.h (the code of bn_partial_kernel), a workgroup per partition of
+//                           PS_BN_ROWS rows and 64 * VEC columns: every lane recomputes ga (ps_epilogue_ga) and xh per element and
+//                           adds ga and ga * xh in fp64 (the product of two fp32 values is exact there): part[P, 2, N].
 //   bn_bwd_finish_kernel    one lane per column adds the partitions ascending from 0.0: dbeta, dgamma, and rstd / k1 / k2 for the
 //                           last pass.
 //   bn_bwd_apply_kernel     one wave per row recomputes ga and writes gz = scale * fmaf(-xh, k2, ga - k1).  A lane reads gy[c] for
@@ -21,7 +20,8 @@
 // registers, 5 matrix sweeps instead of 7) gave the same bits and was measured slower at 59 047 x 256 -- 0.158 ms against 0.100 ms --
 // and is not kept ("Batch-norm layer, training"; why it was slower was not measured).
 #include "ps_common.h"
-#include "row_norm.h"
+#include "col_sums.h"
+#include "row_sweep.h"
 
 namespace {
 
@@ -42,45 +42,12 @@ __global__ __launch_bounds__(256) void bn_bwd_rowscal_kernel(const float *__rest
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t i = (int64_t)blockIdx.x * 4 + wave;
     if (i >= M) return;                                                   // a whole wave
-    const int chunk = 64 * VEC;
     const bool relu = (flags & PS_RELU) != 0;
     const float *zr = z + i * N;
-    const float *gr = gy + i * N;
-    float acc = 0.f;
-    for (int c0 = 0; c0 < N; c0 += chunk) {
-        const int col = c0 + lane * VEC;
-        const bool cact = col < N;
-        float zz[VEC], mm[VEC], sc[VEC], bb[VEC];
-        load_vec<VEC>(zr + col, cact, zz);
-        load_vec<VEC>(mean + col, cact, mm);
-        load_vec<VEC>(scale + col, cact, sc);
-        load_vec<VEC>(beta + col, cact, bb);
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {                                   // a column past N: fmaf(0 - 0, 0, 0) = +0.0
-            const float t = ps_bn_act(zz[e] - mm[e], sc[e], bb[e], relu);
-            acc = fmaf(t, t, acc);
-        }
-    }
-    const float nrm = ps_row_norm(acc);
-    const float c = ps_row_clamp(nrm);
-    acc = 0.f;
-    for (int c0 = 0; c0 < N; c0 += chunk) {
-        const int col = c0 + lane * VEC;
-        const bool cact = col < N;
-        float zz[VEC], gg[VEC], mm[VEC], sc[VEC], bb[VEC];
-        load_vec<VEC>(zr + col, cact, zz);
-        load_vec<VEC>(gr + col, cact, gg);
-        load_vec<VEC>(mean + col, cact, mm);
-        load_vec<VEC>(scale + col, cact, sc);
-        load_vec<VEC>(beta + col, cact, bb);
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            const float t = ps_bn_act(zz[e] - mm[e], sc[e], bb[e], relu);
-            acc = fmaf(gg[e], t / c, acc);
-        }
-    }
-    const float s = ps_wave_sum_f32(acc);
-    if (lane == 0) rows[i] = make_float2(nrm, s);
+    const float2 ns = ps_row_norm_sums<VEC>(N, gy + i * N, [&](int col, bool ok, float (&t)[VEC]) {
+        ps_bn_act_vec<VEC>(zr, mean, scale, beta, col, ok, relu, t);
+    });
+    if (lane == 0) rows[i] = ns;
 }
 
 // part[p, 0, c] = sum of ga[r, c], part[p, 1, c] = sum of ga[r, c] * xh[r, c] over the rows r of partition p (double[P, 2, N])
@@ -89,72 +56,34 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const float *__rest
                                                              const float *__restrict__ mean, const float *__restrict__ var,
                                                              const float *__restrict__ scale, const float *__restrict__ beta, float eps,
                                                              int flags, const float2 *__restrict__ rows, double *__restrict__ part) {
-    __shared__ double sh[3][2][64 * VEC];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int col = (int)blockIdx.y * 64 * VEC + lane * VEC;
+    struct Row { float z[VEC], g[VEC]; float2 rs; };
+    const int col = (int)blockIdx.y * 64 * VEC + (threadIdx.x & 63) * VEC;
     const bool cact = col < N;
     const bool relu = (flags & PS_RELU) != 0, l2 = (flags & PS_L2NORM) != 0;
-    const int64_t p = blockIdx.x;
-    const int64_t r0 = p * PS_BN_ROWS;
-    const int64_t r1 = (r0 + PS_BN_ROWS < M) ? r0 + PS_BN_ROWS : M;
     float mm[VEC], vv[VEC], sc[VEC], bb[VEC], rstd[VEC];
     load_vec<VEC>(mean + col, cact, mm);
     load_vec<VEC>(var + col, cact, vv);
     load_vec<VEC>(scale + col, cact, sc);
     load_vec<VEC>(beta + col, cact, bb);
     rstd_of<VEC>(vv, eps, rstd);
-    double s1[VEC], s2[VEC];
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) { s1[e] = 0.0; s2[e] = 0.0; }
-    for (int64_t r = r0 + wave; r < r1; r += 4 * BN_UNROLL) {
-        float zv[BN_UNROLL][VEC], gv[BN_UNROLL][VEC];
-        float2 rs[BN_UNROLL];
-#pragma unroll
-        for (int t = 0; t < BN_UNROLL; ++t) {
-            const int64_t rr = r + 4 * t;
-            const bool ract = rr < r1;
-            load_vec<VEC>(z + rr * N + col, cact && ract, zv[t]);
-            load_vec<VEC>(gy + rr * N + col, cact && ract, gv[t]);
-            rs[t] = (l2 && ract) ? rows[rr] : make_float2(1.f, 0.f);
-        }
-#pragma unroll
-        for (int t = 0; t < BN_UNROLL; ++t) {
-            if (r + 4 * t >= r1) continue;                                // wave-uniform: a row past the partition adds nothing
-            const float c = ps_row_clamp(rs[t].x);
-            const bool below = rs[t].x < 1e-12f;
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                const float d = zv[t][e] - mm[e];
-                const float tt = ps_bn_act(d, sc[e], bb[e], relu);
-                const float xh = d * rstd[e];
-                const float ga = ps_epilogue_ga(tt, gv[t][e], relu, l2, c, below, rs[t].y);
-                s1[e] += (double)ga;
-                s2[e] += (double)ga * (double)xh;
-            }
-        }
-    }
-    if (wave > 0) {
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            sh[wave - 1][0][lane * VEC + e] = s1[e];
-            sh[wave - 1][1][lane * VEC + e] = s2[e];
-        }
-    }
-    __syncthreads();
-    if (wave == 0 && cact) {
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            double a = s1[e], b = s2[e];
-#pragma unroll
-            for (int w = 0; w < 3; ++w) {
-                a += sh[w][0][lane * VEC + e];
-                b += sh[w][1][lane * VEC + e];
-            }
-            part[(p * 2 + 0) * N + col + e] = a;
-            part[(p * 2 + 1) * N + col + e] = b;
-        }
-    }
+    ps_col_sums_partition<VEC, BN_UNROLL, true>(
+        M, N, blockIdx.x, col,
+        [&](int64_t rr, bool live) {
+            Row row;
+            load_vec<VEC>(z + rr * N + col, cact && live, row.z);
+            load_vec<VEC>(gy + rr * N + col, cact && live, row.g);
+            row.rs = (l2 && live) ? rows[rr] : make_float2(1.f, 0.f);
+            return row;
+        },
+        [&](const Row &row, int e, double &a, double &b) {
+            const float d = row.z[e] - mm[e];
+            const float tt = ps_bn_act(d, sc[e], bb[e], relu);
+            const float xh = d * rstd[e];
+            const float ga = ps_epilogue_ga(tt, row.g[e], relu, l2, ps_row_clamp(row.rs.x), row.rs.x < 1e-12f, row.rs.y);
+            a = (double)ga;
+            b = (double)ga * (double)xh;
+        },
+        part);
 }
 
 // colv = float[3, ldc]: rstd, k1 = dbeta / M, k2 = dgamma / M
@@ -163,13 +92,8 @@ __global__ __launch_bounds__(64) void bn_bwd_finish_kernel(const double *__restr
                                                            float *__restrict__ dbeta, float *__restrict__ colv, int ldc) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= N) return;
-    double S1 = 0.0, S2 = 0.0;
-#pragma unroll 32                                                        // the loads of 32 partitions in flight ahead of the two add chains
-    for (int64_t p = 0; p < P; ++p) {
-        S1 += part[(p * 2 + 0) * N + c];
-        S2 += part[(p * 2 + 1) * N + c];
-    }
-    const float db = (float)S1, dg = (float)S2;
+    const double2 S = ps_col_sums_finish(part, P, N, c);
+    const float db = (float)S.x, dg = (float)S.y;
     if (dbeta) dbeta[c] = db;
     if (dgamma) dgamma[c] = dg;
     colv[c] = 1.0f / sqrtf(var[c] + eps);
@@ -223,7 +147,6 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float *__restri
     }
 }
 
-inline int64_t bn_partitions(int64_t M) { return ps_cdiv(M, PS_BN_ROWS); }
 inline size_t align16(size_t x) { return (x + 15) / 16 * 16; }
 inline int col_ld(int N) { return (N + 3) / 4 * 4; }                     // the three column vectors each start on a 16-byte boundary
 
@@ -234,13 +157,13 @@ struct BnBwdWs {
     float2 *rows;
 };
 inline size_t ws_bytes(int64_t M, int N) {
-    return (size_t)bn_partitions(M) * 2 * (size_t)N * sizeof(double) + 16 + 3 * (size_t)col_ld(N) * sizeof(float) +
+    return (size_t)ps_bn_partitions(M) * 2 * (size_t)N * sizeof(double) + 16 + 3 * (size_t)col_ld(N) * sizeof(float) +
            (size_t)M * sizeof(float2);
 }
 inline BnBwdWs ws_carve(void *workspace, int64_t M, int N) {
     BnBwdWs w;
     w.part = static_cast<double *>(workspace);
-    char *p = reinterpret_cast<char *>(align16(reinterpret_cast<size_t>(w.part + bn_partitions(M) * 2 * (int64_t)N)));
+    char *p = reinterpret_cast<char *>(align16(reinterpret_cast<size_t>(w.part + ps_bn_partitions(M) * 2 * (int64_t)N)));
     w.colv = reinterpret_cast<float *>(p);
     w.rows = reinterpret_cast<float2 *>(p + 3 * (size_t)col_ld(N) * sizeof(float));
     return w;
@@ -253,13 +176,10 @@ int bn_bwd_launch(const float *z, const float *gy, int64_t M, int N, const float
     if (!z || !gy || !mean || !var || !scale || !beta || !workspace) return PS_EINVAL;
     if (reinterpret_cast<size_t>(workspace) % 8 != 0) return PS_EINVAL;
     if (workspace_bytes < ws_bytes(M, N)) return PS_EWORKSPACE;
-    const int64_t P = bn_partitions(M);
+    const int64_t P = ps_bn_partitions(M);
     const int64_t row_blocks = ps_cdiv(M, 4);
     if (row_blocks > 0x7fffffff) return PS_EUNSUPPORTED;                  // every row has a wave of its own
-    size_t align = reinterpret_cast<size_t>(z) | reinterpret_cast<size_t>(gy) | reinterpret_cast<size_t>(mean) |
-                   reinterpret_cast<size_t>(var) | reinterpret_cast<size_t>(scale) | reinterpret_cast<size_t>(beta);
-    if (gz) align |= reinterpret_cast<size_t>(gz);
-    const bool vec4 = (N % 4 == 0) && (align % 16 == 0);
+    const bool vec4 = (N % 4 == 0) && ps_aligned16({z, gy, mean, var, scale, beta, gz});     // gz may be absent
     const bool l2 = (flags & PS_L2NORM) != 0;
     const int64_t col_blocks = ps_cdiv(N, vec4 ? 256 : 64);
     if (col_blocks > 65535) return PS_EUNSUPPORTED;                       // grid.y of the column-sum pass
@@ -267,32 +187,20 @@ int bn_bwd_launch(const float *z, const float *gy, int64_t M, int N, const float
     hipStream_t st = ps_stream(stream);
     const BnBwdWs w = ws_carve(workspace, M, N);
     const int ldc = col_ld(N);
+    const dim3 rows_g((unsigned)row_blocks), cols_g((unsigned)P, (unsigned)col_blocks);
     if (l2) {
-        if (vec4)
-            hipLaunchKernelGGL(bn_bwd_rowscal_kernel<4>, dim3((unsigned)row_blocks), dim3(256), 0, st, z, gy, M, N, mean, scale, beta,
-                               flags, w.rows);
-        else
-            hipLaunchKernelGGL(bn_bwd_rowscal_kernel<1>, dim3((unsigned)row_blocks), dim3(256), 0, st, z, gy, M, N, mean, scale, beta,
-                               flags, w.rows);
+        PS_LAUNCH_VEC(bn_bwd_rowscal_kernel<VEC>, vec4, rows_g, dim3(256), st, z, gy, M, N, mean, scale, beta, flags, w.rows);
         PS_CHECK_LAUNCH();
     }
-    if (vec4)
-        hipLaunchKernelGGL(bn_bwd_partial_kernel<4>, dim3((unsigned)P, (unsigned)col_blocks), dim3(256), 0, st, z, gy, M, N, mean,
-                           var, scale, beta, eps, flags, w.rows, w.part);
-    else
-        hipLaunchKernelGGL(bn_bwd_partial_kernel<1>, dim3((unsigned)P, (unsigned)col_blocks), dim3(256), 0, st, z, gy, M, N, mean,
-                           var, scale, beta, eps, flags, w.rows, w.part);
+    PS_LAUNCH_VEC(bn_bwd_partial_kernel<VEC>, vec4, cols_g, dim3(256), st, z, gy, M, N, mean, var, scale, beta, eps, flags, w.rows,
+                  w.part);
     PS_CHECK_LAUNCH();
     hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3((unsigned)ps_cdiv(N, 64)), dim3(64), 0, st, w.part, P, M, N, var, eps, dgamma, dbeta,
                        w.colv, ldc);
     PS_CHECK_LAUNCH();
     if (gz) {
-        if (vec4)
-            hipLaunchKernelGGL(bn_bwd_apply_kernel<4>, dim3((unsigned)row_blocks), dim3(256), 0, st, z, gy, M, N, mean, scale, beta, flags,
-                               w.rows, w.colv, ldc, gz);
-        else
-            hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, dim3((unsigned)row_blocks), dim3(256), 0, st, z, gy, M, N, mean, scale, beta, flags,
-                               w.rows, w.colv, ldc, gz);
+        PS_LAUNCH_VEC(bn_bwd_apply_kernel<VEC>, vec4, rows_g, dim3(256), st, z, gy, M, N, mean, scale, beta, flags, w.rows, w.colv, ldc,
+                      gz);
         PS_CHECK_LAUNCH();
     }
     return PS_OK;

@@ -7,6 +7,7 @@
 // 16 B-per-lane sweep, up to UNROLL rows in flight); accumulation in fp32 in neighbour order in both.
 #include "ps_common.h"
 #include "pool_row.h"
+#include "row_sweep.h"
 
 namespace {
 
@@ -96,13 +97,7 @@ __global__ __launch_bounds__(256) void importance_pool_kernel(const float *__res
                         const int32_t id = (t < kk) ? __builtin_amdgcn_readlane(myid, t < 64 ? t : 0) : -1;
                         wv[u] = (t < kk) ? __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, myw), t < 64 ? t : 0)) : 0.f;
                         const bool ok = id >= 0 && cact;
-                        if (VEC == 4) {
-                            float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-                            if (ok) q = *reinterpret_cast<const float4 *>(x + (int64_t)id * H + col);
-                            r[u][0] = q.x; r[u][1 % VEC] = q.y; r[u][2 % VEC] = q.z; r[u][3 % VEC] = q.w;
-                        } else {
-                            r[u][0] = ok ? x[(int64_t)id * H + col] : 0.f;
-                        }
+                        load_vec<VEC>(x + (int64_t)id * H + col, ok, r[u]);
                     }
 #pragma unroll
                     for (int u = 0; u < UNROLL; ++u)
@@ -110,13 +105,7 @@ __global__ __launch_bounds__(256) void importance_pool_kernel(const float *__res
                         for (int v = 0; v < VEC; ++v) acc[v] = fmaf(r[u][v], wv[u], acc[v]);
                 }
             }
-            if (cact) {
-                if (VEC == 4) {
-                    *reinterpret_cast<float4 *>(out + i * H + col) = make_float4(acc[0], acc[1 % VEC], acc[2 % VEC], acc[3 % VEC]);
-                } else {
-                    out[i * H + col] = acc[0];
-                }
-            }
+            if (cact) store_vec<VEC>(out + i * H + col, acc);
         }
     }
 }
@@ -156,27 +145,22 @@ extern "C" int ps_importance_pool(const float *x, int64_t N, int H, const int32_
     if (B == 0) return PS_OK;
     if (!x || !ids || !nvalid || !out || (!counts && !wts)) return PS_EINVAL;
     if (max_idx > N - 1) max_idx = N - 1;
-    int64_t grid = ps_cdiv(B, 4);
-    if (grid > 256 * 16) grid = 256 * 16;
     hipStream_t st = ps_stream(stream);
-    const bool vec4 = (H % 4 == 0) && ((reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(out)) % 16 == 0);
+    const bool vec4 = (H % 4 == 0) && ps_aligned16({x, out});
     const char *pe = getenv("PS_POOL_ROWS_PER_WAVE");         // 1: the one-row-per-wave kernel (experiments / cross-check)
     const bool four = vec4 && T <= 64 && !(pe && atoi(pe) == 1);
     if (four) {
-        int64_t g4 = ps_cdiv(B, 16);                           // 4 waves x 4 rows per 256-thread workgroup
-        if (g4 > 256 * 64) g4 = 256 * 64;
+        const dim3 grid4(ps_row4_grid(B));
         if (T <= 16)
-            hipLaunchKernelGGL(importance_pool4_kernel<1>, dim3((unsigned)g4), dim3(256), 0, st, x, H, ids, counts, wts, nvalid, B, T,
-                               max_idx, renorm, out);
+            hipLaunchKernelGGL(importance_pool4_kernel<1>, grid4, dim3(256), 0, st, x, H, ids, counts, wts, nvalid, B, T, max_idx, renorm,
+                               out);
         else
-            hipLaunchKernelGGL(importance_pool4_kernel<4>, dim3((unsigned)g4), dim3(256), 0, st, x, H, ids, counts, wts, nvalid, B, T,
-                               max_idx, renorm, out);
-    } else if (vec4)
-        hipLaunchKernelGGL(importance_pool_kernel<4>, dim3((unsigned)grid), dim3(256), 0, st, x, H, ids, counts, wts,
-                           nvalid, B, T, max_idx, renorm, out);
-    else
-        hipLaunchKernelGGL(importance_pool_kernel<1>, dim3((unsigned)grid), dim3(256), 0, st, x, H, ids, counts, wts,
-                           nvalid, B, T, max_idx, renorm, out);
+            hipLaunchKernelGGL(importance_pool4_kernel<4>, grid4, dim3(256), 0, st, x, H, ids, counts, wts, nvalid, B, T, max_idx, renorm,
+                               out);
+    } else {
+        PS_LAUNCH_VEC(importance_pool_kernel<VEC>, vec4, dim3(ps_row_grid(B)), dim3(256), st, x, H, ids, counts, wts, nvalid, B, T,
+                      max_idx, renorm, out);
+    }
     PS_CHECK_LAUNCH();
     return PS_OK;
 }

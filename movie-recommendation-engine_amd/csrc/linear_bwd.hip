@@ -15,11 +15,11 @@
 //                         workgroups of the first tile column add the bias gradient's chain from the staged g.  One partition:
 //                         the tile goes to dW.  Several: to the workspace, and a second launch adds every element's partials in
 //                         partition order.
-// ps_linear_epilogue_bwd  one wave per row, the sweeps and the norm of ps_bn_apply (row_norm.h).  Three sweeps over the row: the
-//                         sum of squares of t, s = sum g y, the output; a lane reads g[c] for the last time before it writes
-//                         gz[c], so gz may be g.
+// ps_linear_epilogue_bwd  one wave per row, the sweeps and the norm of ps_bn_apply (row_sweep.h).  Three sweeps over the row: the
+//                         sum of squares of t and s = sum g y (ps_row_norm_sums), then the output; a lane reads g[c] for the last
+//                         time before it writes gz[c], so gz may be g.
 #include "ps_common.h"
-#include "row_norm.h"
+#include "row_sweep.h"
 
 namespace {
 
@@ -191,27 +191,10 @@ __global__ __launch_bounds__(256) void epilogue_bwd_kernel(const float *t, const
         float c = 1.f, s = 0.f;
         bool below = false;
         if (l2) {
-            float acc = 0.f;
-            for (int c0 = 0; c0 < N; c0 += chunk) {
-                const int col = c0 + lane * VEC;
-                float tt[VEC];
-                load_vec<VEC>(tr + col, col < N, tt);
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) acc = fmaf(tt[e], tt[e], acc);
-            }
-            const float nrm = ps_row_norm(acc);
-            c = ps_row_clamp(nrm);
-            below = nrm < 1e-12f;
-            acc = 0.f;
-            for (int c0 = 0; c0 < N; c0 += chunk) {
-                const int col = c0 + lane * VEC;
-                float tt[VEC], gg[VEC];
-                load_vec<VEC>(tr + col, col < N, tt);
-                load_vec<VEC>(gr + col, col < N, gg);
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) acc = fmaf(gg[e], tt[e] / c, acc);
-            }
-            s = ps_wave_sum_f32(acc);
+            const float2 ns = ps_row_norm_sums<VEC>(N, gr, [&](int col, bool ok, float (&tt)[VEC]) { load_vec<VEC>(tr + col, ok, tt); });
+            c = ps_row_clamp(ns.x);
+            below = ns.x < 1e-12f;
+            s = ns.y;
         }
         for (int c0 = 0; c0 < N; c0 += chunk) {
             const int col = c0 + lane * VEC;
@@ -224,11 +207,6 @@ __global__ __launch_bounds__(256) void epilogue_bwd_kernel(const float *t, const
             store_vec<VEC>(zr + col, o);
         }
     }
-}
-
-inline unsigned row_grid(int64_t B) {          // 4 waves (rows) per workgroup; beyond 16 384 waves the rows are strided over
-    int64_t grid = ps_cdiv(B, 4);
-    return (unsigned)(grid > 256 * 16 ? 256 * 16 : grid);
 }
 
 }  // namespace
@@ -271,7 +249,7 @@ static int wgrad_launch(const float *g, int64_t M, int N, const float *x, int K,
             db_stride = N;
         }
     }
-    const bool vec4 = N % 4 == 0 && K % 4 == 0 && (reinterpret_cast<size_t>(g) | reinterpret_cast<size_t>(x)) % 16 == 0;
+    const bool vec4 = N % 4 == 0 && K % 4 == 0 && ps_aligned16({g, x});
     const dim3 grid((unsigned)(tiles_n * tiles_k), (unsigned)parts);
     if (vec4)
         hipLaunchKernelGGL(wgrad_kernel<true>, grid, dim3(256), 0, st, g, x, M, N, K, P, tiles_k, dst, dst_stride, dbdst, db_stride);
@@ -310,11 +288,8 @@ extern "C" int ps_linear_epilogue_bwd(const float *t, const float *g, int64_t M,
         if (gz != g && ps_copy_async(gz, g, (size_t)M * (size_t)N * sizeof(float), st) != hipSuccess) return PS_ELAUNCH;
         return PS_OK;
     }
-    const bool vec4 = (N % 4 == 0) && ((reinterpret_cast<size_t>(t) | reinterpret_cast<size_t>(g) | reinterpret_cast<size_t>(gz)) % 16 == 0);
-    if (vec4)
-        hipLaunchKernelGGL(epilogue_bwd_kernel<4>, dim3(row_grid(M)), dim3(256), 0, st, t, g, M, N, flags, gz);
-    else
-        hipLaunchKernelGGL(epilogue_bwd_kernel<1>, dim3(row_grid(M)), dim3(256), 0, st, t, g, M, N, flags, gz);
+    const bool vec4 = (N % 4 == 0) && ps_aligned16({t, g, gz});
+    PS_LAUNCH_VEC(epilogue_bwd_kernel<VEC>, vec4, dim3(ps_row_grid(M)), dim3(256), st, t, g, M, N, flags, gz);
     PS_CHECK_LAUNCH();
     return PS_OK;
 }

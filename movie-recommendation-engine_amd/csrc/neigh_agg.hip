@@ -1,51 +1,15 @@
 // neigh_agg.hip -- the neighbour gathers of AttentionAggregator and MaxPoolingAggregator on gfx950 (L2/HBM-bound row gathers).
 //
 // Replaces the per-node loops of the reference's model/aggregators.py:131-158 (attention scores + softmax) and :195-209 (max over
-// the neighbours' transformed rows).  Same shape as importance_pool_kernel (csrc/importance_pool.hip): one wave per output row,
-// a neighbour row is one coalesced 16 B-per-lane sweep (scalar sweep for H % 4 != 0 or unaligned pointers), up to UNROLL neighbour
+// the neighbours' transformed rows).  The sweep of importance_pool_kernel (csrc/importance_pool.hip), from row_sweep.h: one wave per
+// output row, a neighbour row is one coalesced 16 B-per-lane sweep (scalar sweep for H % 4 != 0 or unaligned pointers), up to UNROLL neighbour
 // rows in flight, grid-stride over the rows, no atomics, no LDS.  A slot is kept iff j < min(nvalid[i], T) and 0 <= ids[i,j] < N.
 #include "ps_common.h"
+#include "row_sweep.h"
 
 namespace {
 
 constexpr int UNROLL = 8;
-
-#define PS_DPP_F32(v, ctrl, rows) \
-    __builtin_bit_cast(float, __builtin_amdgcn_update_dpp((int)0xff800000u, __builtin_bit_cast(int, v), (ctrl), (rows), 0xf, false))
-// wave-wide maximum, result in every lane (the DPP steps of ps_wave_sum_f32; a lane a step does not reach reads -inf).
-// fmaxf drops a NaN operand: a NaN score surfaces through expf in the softmax, not through the maximum.
-__device__ __forceinline__ float wave_max_f32(float v) {
-    v = fmaxf(v, PS_DPP_F32(v, 0xB1, 0xf));
-    v = fmaxf(v, PS_DPP_F32(v, 0x4E, 0xf));
-    v = fmaxf(v, PS_DPP_F32(v, 0x141, 0xf));
-    v = fmaxf(v, PS_DPP_F32(v, 0x140, 0xf));
-    v = fmaxf(v, PS_DPP_F32(v, 0x142, 0xa));
-    v = fmaxf(v, PS_DPP_F32(v, 0x143, 0xc));
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-#undef PS_DPP_F32
-
-// the VEC floats at p (zeros when !ok: nothing is requested)
-template <int VEC>
-__device__ __forceinline__ void load_vec(const float *__restrict__ p, bool ok, float (&r)[VEC]) {
-    if (VEC == 4) {
-        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (ok) q = *reinterpret_cast<const float4 *>(p);
-        r[0] = q.x; r[1 % VEC] = q.y; r[2 % VEC] = q.z; r[3 % VEC] = q.w;
-    } else {
-        r[0] = ok ? p[0] : 0.f;
-    }
-}
-
-// the kept id of slot jj of row i (-1: not kept)
-__device__ __forceinline__ int32_t kept_id(const int32_t *__restrict__ ids, int64_t i, int T, int jj, int k, int64_t N) {
-    int32_t id = -1;
-    if (jj < k) {
-        id = ids[i * T + jj];
-        if (id < 0 || (int64_t)id >= N) id = -1;
-    }
-    return id;
-}
 
 // ---- attention weights ------------------------------------------------------------------------------------------------------
 // attn[i, j] = softmax_j( sum_c w2[c] * relu(u[i, c] + v[ids[i, j], c]) ) over the kept slots of row i, +0.0 elsewhere.
@@ -122,7 +86,7 @@ __global__ __launch_bounds__(256) void attention_weights_kernel(const float *__r
             if (small) s0 = mys;
             else if (j0 + lane < k) attn[i * T + j0 + lane] = mys;
         }
-        m = wave_max_f32(m);
+        m = ps_wave_max_f32(m);
         // softmax over the kept slots: exp(s - max) / sum; a row that keeps nothing has sum 0 and is written as zeros
         if (small) {
             const bool kept = lane < k && kept_id(ids, i, T, lane, k, N) >= 0;
@@ -198,17 +162,9 @@ __global__ __launch_bounds__(256) void gather_max_kernel(const float *__restrict
                         }
                 }
             }
-            if (cact) {
-                if (VEC == 4) *reinterpret_cast<float4 *>(out + i * H + col) = make_float4(acc[0], acc[1 % VEC], acc[2 % VEC], acc[3 % VEC]);
-                else out[i * H + col] = acc[0];
-            }
+            if (cact) store_vec<VEC>(out + i * H + col, acc);
         }
     }
-}
-
-inline unsigned row_grid(int64_t B) {          // 4 waves (rows) per workgroup; beyond 16 384 waves the rows are strided over
-    int64_t grid = ps_cdiv(B, 4);
-    return (unsigned)(grid > 256 * 16 ? 256 * 16 : grid);
 }
 
 }  // namespace
@@ -219,12 +175,8 @@ extern "C" int ps_attention_weights(const float *u, const float *v, int64_t N, i
     if (B == 0) return PS_OK;                                 // before the pointers: an empty tensor's base is NULL
     if (!u || !v || !w2 || !ids || !nvalid || !attn) return PS_EINVAL;
     hipStream_t st = ps_stream(stream);
-    const bool vec4 = (Hd % 4 == 0) &&
-                      ((reinterpret_cast<size_t>(u) | reinterpret_cast<size_t>(v) | reinterpret_cast<size_t>(w2)) % 16 == 0);
-    if (vec4)
-        hipLaunchKernelGGL(attention_weights_kernel<4>, dim3(row_grid(B)), dim3(256), 0, st, u, v, N, Hd, w2, ids, nvalid, B, T, attn);
-    else
-        hipLaunchKernelGGL(attention_weights_kernel<1>, dim3(row_grid(B)), dim3(256), 0, st, u, v, N, Hd, w2, ids, nvalid, B, T, attn);
+    const bool vec4 = (Hd % 4 == 0) && ps_aligned16({u, v, w2});
+    PS_LAUNCH_VEC(attention_weights_kernel<VEC>, vec4, dim3(ps_row_grid(B)), dim3(256), st, u, v, N, Hd, w2, ids, nvalid, B, T, attn);
     PS_CHECK_LAUNCH();
     return PS_OK;
 }
@@ -235,11 +187,8 @@ extern "C" int ps_gather_max(const float *x, int64_t N, int H, const int32_t *id
     if (B == 0) return PS_OK;                                 // before the pointers: an empty tensor's base is NULL
     if (!x || !ids || !nvalid || !out) return PS_EINVAL;
     hipStream_t st = ps_stream(stream);
-    const bool vec4 = (H % 4 == 0) && ((reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(out)) % 16 == 0);
-    if (vec4)
-        hipLaunchKernelGGL(gather_max_kernel<4>, dim3(row_grid(B)), dim3(256), 0, st, x, N, H, ids, nvalid, B, T, out);
-    else
-        hipLaunchKernelGGL(gather_max_kernel<1>, dim3(row_grid(B)), dim3(256), 0, st, x, N, H, ids, nvalid, B, T, out);
+    const bool vec4 = (H % 4 == 0) && ps_aligned16({x, out});
+    PS_LAUNCH_VEC(gather_max_kernel<VEC>, vec4, dim3(ps_row_grid(B)), dim3(256), st, x, N, H, ids, nvalid, B, T, out);
     PS_CHECK_LAUNCH();
     return PS_OK;
 }

@@ -6,65 +6,15 @@
 // owns a destination row (or one SEG-slot segment of a hub row) and sweeps the source rows its slots name exactly as the forward
 // kernels sweep theirs: 16 bytes per lane (a scalar sweep for H % 4 != 0 or unaligned pointers), UNROLL rows in flight, no LDS.
 // include/pinsage_hip.h states the arithmetic; tests/helpers/agg_bwd_cases.py restates it bit for bit.
-#include <initializer_list>
 #include "ps_common.h"
 #include "pool_row.h"
+#include "row_sweep.h"
 
 namespace {
 
 constexpr int UNROLL = 8;
 constexpr int SEG = 128;                       // slots per segment of S(r): ps_gather_bwd_segment()
 constexpr int DW_ROWS = 128;                   // target rows per partition of the dw2 sum
-
-template <int VEC>
-__device__ __forceinline__ void load_vec(const float *__restrict__ p, bool ok, float (&r)[VEC]) {
-    if (VEC == 4) {
-        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (ok) q = *reinterpret_cast<const float4 *>(p);
-        r[0] = q.x; r[1 % VEC] = q.y; r[2 % VEC] = q.z; r[3 % VEC] = q.w;
-    } else {
-        r[0] = ok ? p[0] : 0.f;
-    }
-}
-template <int VEC>
-__device__ __forceinline__ void load_veci(const int32_t *__restrict__ p, bool ok, int32_t (&r)[VEC]) {
-    if (VEC == 4) {
-        int4 q = make_int4(-1, -1, -1, -1);
-        if (ok) q = *reinterpret_cast<const int4 *>(p);
-        r[0] = q.x; r[1 % VEC] = q.y; r[2 % VEC] = q.z; r[3 % VEC] = q.w;
-    } else {
-        r[0] = ok ? p[0] : -1;
-    }
-}
-template <int VEC>
-__device__ __forceinline__ void store_vec(float *__restrict__ p, const float (&r)[VEC]) {
-    if (VEC == 4) *reinterpret_cast<float4 *>(p) = make_float4(r[0], r[1 % VEC], r[2 % VEC], r[3 % VEC]);
-    else p[0] = r[0];
-}
-template <int VEC>
-__device__ __forceinline__ void store_veci(int32_t *__restrict__ p, const int32_t (&r)[VEC]) {
-    if (VEC == 4) *reinterpret_cast<int4 *>(p) = make_int4(r[0], r[1 % VEC], r[2 % VEC], r[3 % VEC]);
-    else p[0] = r[0];
-}
-
-__device__ __forceinline__ float lane_f32(float v, int t) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), t));
-}
-
-// the kept id of slot jj of row i (-1: not kept): the keep rule of csrc/neigh_agg.hip
-__device__ __forceinline__ int32_t kept_id(const int32_t *__restrict__ ids, int64_t i, int T, int jj, int k, int64_t N) {
-    int32_t id = -1;
-    if (jj < k) {
-        id = ids[i * T + jj];
-        if (id < 0 || (int64_t)id >= N) id = -1;
-    }
-    return id;
-}
-
-inline unsigned row_grid(int64_t B) {          // 4 waves per workgroup; beyond 16 384 waves the items are strided over
-    int64_t grid = ps_cdiv(B, 4);
-    return (unsigned)(grid > 256 * 16 ? 256 * 16 : (grid < 1 ? 1 : grid));
-}
 
 // ---- the weights ps_importance_pool applies ----------------------------------------------------------------------------------
 // 16-lane layout (T <= 64): pool4_weights, the code of the forward itself
@@ -314,14 +264,9 @@ inline size_t transposed_bytes(int64_t B, int T, int H) { return 256 + ps_align2
 
 template <int MODE>
 int launch_transposed(TArgs a, bool vec4, hipStream_t st) {
-    const unsigned grid = row_grid(a.N + 2 * a.nblk), grid2 = row_grid(a.N);
-    if (vec4) {
-        hipLaunchKernelGGL((transposed_kernel<4, MODE>), dim3(grid), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(combine_kernel<4>, dim3(grid2), dim3(256), 0, st, a);
-    } else {
-        hipLaunchKernelGGL((transposed_kernel<1, MODE>), dim3(grid), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(combine_kernel<1>, dim3(grid2), dim3(256), 0, st, a);
-    }
+    PS_LAUNCH_VEC((transposed_kernel<VEC, MODE>), vec4, dim3(ps_row_grid(a.N + 2 * a.nblk)), dim3(256), st, a);
+    PS_CHECK_LAUNCH();
+    PS_LAUNCH_VEC(combine_kernel<VEC>, vec4, dim3(ps_row_grid(a.N)), dim3(256), st, a);
     PS_CHECK_LAUNCH();
     return PS_OK;
 }
@@ -525,12 +470,6 @@ __global__ __launch_bounds__(256) void dw2_final_kernel(const float *__restrict_
     dw2[c] = acc;
 }
 
-inline bool aligned16(std::initializer_list<const void *> ps) {
-    size_t m = 0;
-    for (const void *p : ps) m |= reinterpret_cast<size_t>(p);
-    return m % 16 == 0;
-}
-
 }  // namespace
 
 extern "C" int ps_pool_weights(const int32_t *ids, const int32_t *counts, const float *wts, const int32_t *nvalid, int64_t B, int T,
@@ -542,16 +481,13 @@ extern "C" int ps_pool_weights(const int32_t *ids, const int32_t *counts, const 
     const char *pe = getenv("PS_POOL_ROWS_PER_WAVE");         // ps_importance_pool's switch: 1 = the wave layout everywhere
     const bool four = lanes == 16 && T <= 64 && !(pe && atoi(pe) == 1);
     if (four) {
-        int64_t g4 = ps_cdiv(B, 16);
-        if (g4 > 256 * 64) g4 = 256 * 64;
+        const dim3 grid4(ps_row4_grid(B));
         if (T <= 16)
-            hipLaunchKernelGGL(pool_weights4_kernel<1>, dim3((unsigned)g4), dim3(256), 0, st, ids, counts, wts, nvalid, B, T, max_idx,
-                               renorm, w_eff);
+            hipLaunchKernelGGL(pool_weights4_kernel<1>, grid4, dim3(256), 0, st, ids, counts, wts, nvalid, B, T, max_idx, renorm, w_eff);
         else
-            hipLaunchKernelGGL(pool_weights4_kernel<4>, dim3((unsigned)g4), dim3(256), 0, st, ids, counts, wts, nvalid, B, T, max_idx,
-                               renorm, w_eff);
+            hipLaunchKernelGGL(pool_weights4_kernel<4>, grid4, dim3(256), 0, st, ids, counts, wts, nvalid, B, T, max_idx, renorm, w_eff);
     } else {
-        hipLaunchKernelGGL(pool_weights_kernel, dim3(row_grid(B)), dim3(256), 0, st, ids, counts, wts, nvalid, B, T, max_idx, renorm,
+        hipLaunchKernelGGL(pool_weights_kernel, dim3(ps_row_grid(B)), dim3(256), 0, st, ids, counts, wts, nvalid, B, T, max_idx, renorm,
                            w_eff);
     }
     PS_CHECK_LAUNCH();
@@ -580,7 +516,7 @@ extern "C" int ps_gather_bwd(const int64_t *rptr, const int32_t *slots, int64_t 
     if (workspace_bytes < transposed_bytes(B, T, H)) return PS_EINVAL;
     TArgs a{rptr, slots, N, T, coef, arg, g, B, H, nullptr, nullptr, gx, reinterpret_cast<float *>(ps_ws_base(workspace)),
             seg_blocks(B, T)};
-    const bool vec4 = H % 4 == 0 && aligned16({g, gx, arg});
+    const bool vec4 = H % 4 == 0 && ps_aligned16({g, gx, arg});
     return coef ? launch_transposed<0>(a, vec4, st) : launch_transposed<1>(a, vec4, st);
 }
 
@@ -590,11 +526,8 @@ extern "C" int ps_gather_max_arg(const float *x, int64_t N, int H, const int32_t
     if (B == 0) return PS_OK;
     if (!x || !ids || !nvalid || !out || !arg) return PS_EINVAL;
     hipStream_t st = ps_stream(stream);
-    const bool vec4 = H % 4 == 0 && aligned16({x, out, arg});
-    if (vec4)
-        hipLaunchKernelGGL(gather_max_arg_kernel<4>, dim3(row_grid(B)), dim3(256), 0, st, x, N, H, ids, nvalid, B, T, out, arg);
-    else
-        hipLaunchKernelGGL(gather_max_arg_kernel<1>, dim3(row_grid(B)), dim3(256), 0, st, x, N, H, ids, nvalid, B, T, out, arg);
+    const bool vec4 = H % 4 == 0 && ps_aligned16({x, out, arg});
+    PS_LAUNCH_VEC(gather_max_arg_kernel<VEC>, vec4, dim3(ps_row_grid(B)), dim3(256), st, x, N, H, ids, nvalid, B, T, out, arg);
     PS_CHECK_LAUNCH();
     return PS_OK;
 }
@@ -615,14 +548,12 @@ extern "C" int ps_attention_bwd_rows(const float *x, int64_t N, int H, const flo
     float *share = reinterpret_cast<float *>(ps_ws_base(workspace));
     float *parts = share + B * Hd;
     const int64_t P = ps_cdiv(B, DW_ROWS);
-    const bool vec4 = H % 4 == 0 && Hd % 4 == 0 && aligned16({x, u, v, w2, g, du});
-    if (vec4)
-        hipLaunchKernelGGL(attention_bwd_rows_kernel<4>, dim3(row_grid(B)), dim3(256), 0, st, x, N, H, u, v, Hd, w2, ids, nvalid, attn,
-                           g, B, T, ds, du, share);
-    else
-        hipLaunchKernelGGL(attention_bwd_rows_kernel<1>, dim3(row_grid(B)), dim3(256), 0, st, x, N, H, u, v, Hd, w2, ids, nvalid, attn,
-                           g, B, T, ds, du, share);
+    const bool vec4 = H % 4 == 0 && Hd % 4 == 0 && ps_aligned16({x, u, v, w2, g, du});
+    PS_LAUNCH_VEC(attention_bwd_rows_kernel<VEC>, vec4, dim3(ps_row_grid(B)), dim3(256), st, x, N, H, u, v, Hd, w2, ids, nvalid, attn, g,
+                  B, T, ds, du, share);
+    PS_CHECK_LAUNCH();
     hipLaunchKernelGGL(dw2_partition_kernel, dim3((unsigned)P, (unsigned)ps_cdiv(Hd, 256)), dim3(256), 0, st, share, B, Hd, parts);
+    PS_CHECK_LAUNCH();
     hipLaunchKernelGGL(dw2_final_kernel, dim3((unsigned)ps_cdiv(Hd, 256)), dim3(256), 0, st, parts, P, Hd, dw2);
     PS_CHECK_LAUNCH();
     return PS_OK;
@@ -642,6 +573,6 @@ extern "C" int ps_attention_bwd_cols(const int64_t *rptr, const int32_t *slots, 
     if (!rptr || !slots || !ds || !u || !v || !w2 || !workspace) return PS_EINVAL;
     if (workspace_bytes < transposed_bytes(B, T, Hd)) return PS_EINVAL;
     TArgs a{rptr, slots, N, T, ds, nullptr, u, B, Hd, v, w2, dv, reinterpret_cast<float *>(ps_ws_base(workspace)), seg_blocks(B, T)};
-    const bool vec4 = Hd % 4 == 0 && aligned16({u, v, w2, dv});
+    const bool vec4 = Hd % 4 == 0 && ps_aligned16({u, v, w2, dv});
     return launch_transposed<2>(a, vec4, st);
 }

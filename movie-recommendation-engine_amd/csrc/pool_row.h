@@ -6,22 +6,7 @@
 namespace {
 
 template <int CTRL>
-__device__ __forceinline__ int row_bcast_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false); }
-__device__ __forceinline__ int row16_sum_i32(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, true);
-    return v;
-}
-__device__ __forceinline__ float row16_sum_f32(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xf, 0xf, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xf, 0xf, true));
-    return v;
-}
-
+__device__ __forceinline__ int row_bcast_i32(int v) { return ps_dpp_step<CTRL, 0xf, false>(v, 0); }
 // Does row i keep at least one neighbour (j < nvalid[i], 0 <= ids[i, j] <= max_idx)?  The keep test of pool4_row below: a row that
 // keeps none is pooled to +0.0 in every column without touching x.
 __device__ __forceinline__ bool pool_row_keeps(const int32_t *__restrict__ ids, const int32_t *__restrict__ nvalid, int64_t i, int T,
@@ -67,7 +52,7 @@ __device__ __forceinline__ void pool4_weights(const int32_t *__restrict__ ids, c
     int tot = 0;
 #pragma unroll
     for (int p = 0; p < PAGES; ++p) tot += (p * 16 + l < k) ? cn[p] : 0;
-    tot = row16_sum_i32(tot);
+    tot = ps_row16_sum_i32(tot);
     float wsum = 0.f;
 #pragma unroll
     for (int p = 0; p < PAGES; ++p) {
@@ -76,7 +61,7 @@ __device__ __forceinline__ void pool4_weights(const int32_t *__restrict__ ids, c
         id[p] = keep ? id[p] : -1;
         wsum += w[p];
     }
-    wsum = row16_sum_f32(wsum);
+    wsum = ps_row16_sum_f32(wsum);
     if (renorm && wsum > 0.f) {
 #pragma unroll
         for (int p = 0; p < PAGES; ++p) w[p] = id[p] >= 0 ? w[p] / wsum : 0.f;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include <initializer_list>
 #include "../../include/pinsage_hip.h"
 
 #define PS_WAVE 64
@@ -38,6 +39,36 @@ static inline int64_t ps_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // workspaces are carved in 256-byte units from the first 256-byte boundary at or after the caller's pointer
 static inline size_t ps_align256(size_t x) { return (x + 255) / 256 * 256; }
 static inline char *ps_ws_base(void *workspace) { return reinterpret_cast<char *>(ps_align256(reinterpret_cast<size_t>(workspace))); }
+
+// ---- launch glue of the row and column kernels ----
+// one wave per row, 4 waves per workgroup; beyond 16 384 waves the kernel strides over the rows (no caller passes rows < 1)
+static inline unsigned ps_row_grid(int64_t rows) {
+    const int64_t grid = ps_cdiv(rows, 4);
+    return (unsigned)(grid > 256 * 16 ? 256 * 16 : (grid < 1 ? 1 : grid));
+}
+// four rows per wave (a 16-lane group each: csrc/pool_row.h), 16 per workgroup
+static inline unsigned ps_row4_grid(int64_t rows) {
+    const int64_t grid = ps_cdiv(rows, 16);
+    return (unsigned)(grid > 256 * 64 ? 256 * 64 : (grid < 1 ? 1 : grid));
+}
+// may every pointer be the base of 16-byte requests?  A null (absent) pointer does not object.
+static inline bool ps_aligned16(std::initializer_list<const void *> ps) {
+    size_t m = 0;
+    for (const void *p : ps) m |= reinterpret_cast<size_t>(p);
+    return m % 16 == 0;
+}
+// A kernel template's 16-byte or 4-byte form: KERNEL is written with VEC where the floats per lane go, e.g.
+// PS_LAUNCH_VEC(bn_apply_kernel<VEC>, vec4, ...) or PS_LAUNCH_VEC((transposed_kernel<VEC, MODE>), vec4, ...).
+#define PS_LAUNCH_VEC(KERNEL, vec4, grid, block, stream, ...)                     \
+    do {                                                                          \
+        if (vec4) {                                                               \
+            constexpr int VEC = 4;                                                \
+            hipLaunchKernelGGL(KERNEL, grid, block, 0, stream, __VA_ARGS__);      \
+        } else {                                                                  \
+            constexpr int VEC = 1;                                                \
+            hipLaunchKernelGGL(KERNEL, grid, block, 0, stream, __VA_ARGS__);      \
+        }                                                                         \
+    } while (0)
 
 // Fills and device-to-device copies inside an entry point are plain kernels (ps_fill_async / ps_copy_async), not
 // hipMemsetAsync / hipMemcpyAsync.  Captured into a hipGraph those two become memset / memcpy NODES.  Observed on the MI355X
@@ -129,25 +160,47 @@ __device__ __forceinline__ void ps_wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// Wave-wide sums, result in every lane.  DPP only (quad_perm, row_half_mirror, row_mirror, row_bcast:15 / :31, then a
-// v_readlane of lane 63): __shfl_xor goes through the LDS crossbar, which all waves of a CU share.
-#define PS_DPP_MOV(v, ctrl, rows) __builtin_amdgcn_update_dpp(0, (v), (ctrl), (rows), 0xf, true)
-__device__ __forceinline__ int ps_wave_sum_i32(int v) {
-    v += PS_DPP_MOV(v, 0xB1, 0xf);
-    v += PS_DPP_MOV(v, 0x4E, 0xf);
-    v += PS_DPP_MOV(v, 0x141, 0xf);
-    v += PS_DPP_MOV(v, 0x140, 0xf);
-    v += PS_DPP_MOV(v, 0x142, 0xa);
-    v += PS_DPP_MOV(v, 0x143, 0xc);
-    return __builtin_amdgcn_readlane(v, 63);
+// Reductions over the 16 lanes of a DPP row and over the wave.  DPP only (quad_perm, row_half_mirror, row_mirror, then
+// row_bcast:15 / :31 and a v_readlane of lane 63): __shfl_xor goes through the LDS crossbar, which all waves of a CU share.
+//
+// One step: lane l's copy of the v of the lane that CTRL names, taken in the rows of mask ROWS.  A lane that the step does not
+// reach reads 0 under BOUND (bound_ctrl) and fill otherwise.  T is int or float.
+template <int CTRL, int ROWS, bool BOUND, typename T>
+__device__ __forceinline__ T ps_dpp_step(T v, T fill) {
+    static_assert(sizeof(T) == 4, "a DPP step moves one 32-bit register");
+    return __builtin_bit_cast(
+        T, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, fill), __builtin_bit_cast(int, v), CTRL, ROWS, 0xf, BOUND));
 }
-__device__ __forceinline__ float ps_wave_sum_f32(float v) {
-    v += __builtin_bit_cast(float, PS_DPP_MOV(__builtin_bit_cast(int, v), 0xB1, 0xf));
-    v += __builtin_bit_cast(float, PS_DPP_MOV(__builtin_bit_cast(int, v), 0x4E, 0xf));
-    v += __builtin_bit_cast(float, PS_DPP_MOV(__builtin_bit_cast(int, v), 0x141, 0xf));
-    v += __builtin_bit_cast(float, PS_DPP_MOV(__builtin_bit_cast(int, v), 0x140, 0xf));
-    v += __builtin_bit_cast(float, PS_DPP_MOV(__builtin_bit_cast(int, v), 0x142, 0xa));
-    v += __builtin_bit_cast(float, PS_DPP_MOV(__builtin_bit_cast(int, v), 0x143, 0xc));
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+struct PsSum {                                 // v + the other lane's v; an unreached lane adds 0
+    template <int CTRL, int ROWS, typename T>
+    static __device__ __forceinline__ T step(T v) { return v + ps_dpp_step<CTRL, ROWS, true>(v, T(0)); }
+};
+struct PsMax {                                 // fmaxf, which drops a NaN operand; an unreached lane offers -inf
+    template <int CTRL, int ROWS>
+    static __device__ __forceinline__ float step(float v) {
+        return fmaxf(v, ps_dpp_step<CTRL, ROWS, false>(v, __builtin_bit_cast(float, 0xff800000u)));
+    }
+};
+// over the 16 lanes of a row, result in each of them
+template <typename OP, typename T>
+__device__ __forceinline__ T ps_row16_reduce(T v) {
+    v = OP::template step<0xB1, 0xf>(v);       // quad_perm [1, 0, 3, 2]
+    v = OP::template step<0x4E, 0xf>(v);       // quad_perm [2, 3, 0, 1]
+    v = OP::template step<0x141, 0xf>(v);      // row_half_mirror
+    v = OP::template step<0x140, 0xf>(v);      // row_mirror
+    return v;
 }
-#undef PS_DPP_MOV
+// over the wave, result in every lane
+template <typename OP, typename T>
+__device__ __forceinline__ T ps_wave_reduce(T v) {
+    v = ps_row16_reduce<OP>(v);
+    v = OP::template step<0x142, 0xa>(v);      // row_bcast:15 into rows 1 and 3
+    v = OP::template step<0x143, 0xc>(v);      // row_bcast:31 into rows 2 and 3
+    return __builtin_bit_cast(T, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+__device__ __forceinline__ int ps_row16_sum_i32(int v) { return ps_row16_reduce<PsSum>(v); }
+__device__ __forceinline__ float ps_row16_sum_f32(float v) { return ps_row16_reduce<PsSum>(v); }
+__device__ __forceinline__ int ps_wave_sum_i32(int v) { return ps_wave_reduce<PsSum>(v); }
+__device__ __forceinline__ float ps_wave_sum_f32(float v) { return ps_wave_reduce<PsSum>(v); }
+// a NaN score surfaces through expf in the softmax (csrc/neigh_agg.hip), not through the maximum
+__device__ __forceinline__ float ps_wave_max_f32(float v) { return ps_wave_reduce<PsMax>(v); }

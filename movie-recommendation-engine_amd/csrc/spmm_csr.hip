@@ -8,6 +8,7 @@
 // completely inside one slice is stored; a row cut by a slice boundary adds its partial sums with fp32 atomics
 // (PyG's scatter-add is atomic too); out is zeroed first (empty rows, atomics).
 #include "ps_common.h"
+#include "row_sweep.h"
 
 namespace {
 
@@ -57,13 +58,7 @@ __global__ __launch_bounds__(256) void spmm_csr_kernel(const int64_t *__restrict
                         const int32_t id = (t < kk) ? __builtin_amdgcn_readlane(myid, tl) : -1;
                         wv[u] = (t < kk) ? __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, myw), tl)) : 0.f;
                         const bool ok = id >= 0 && (int64_t)id < N && cact;       // a source id outside x is skipped, never read
-                        if (VEC == 4) {
-                            float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-                            if (ok) q = *reinterpret_cast<const float4 *>(x + (int64_t)id * H + cc);
-                            rr[u][0] = q.x; rr[u][1 % VEC] = q.y; rr[u][2 % VEC] = q.z; rr[u][3 % VEC] = q.w;
-                        } else {
-                            rr[u][0] = ok ? x[(int64_t)id * H + cc] : 0.f;
-                        }
+                        load_vec<VEC>(x + (int64_t)id * H + cc, ok, rr[u]);
                     }
 #pragma unroll
                     for (int u = 0; u < UNROLL; ++u)
@@ -98,9 +93,8 @@ extern "C" int ps_spmm_csr(const int64_t *rowptr, const int32_t *col, const floa
     const int64_t waves = ps_cdiv(E, SLICE);
     const int64_t grid = ps_cdiv(waves, 4);
     if (grid > 0x7fffffff) return PS_EUNSUPPORTED;
-    const bool vec4 = (H % 4 == 0) && ((reinterpret_cast<size_t>(x) | reinterpret_cast<size_t>(out)) % 16 == 0);
-    if (vec4) hipLaunchKernelGGL(spmm_csr_kernel<4>, dim3((unsigned)grid), dim3(256), 0, st, rowptr, col, val, x, N, H, V, E, out);
-    else hipLaunchKernelGGL(spmm_csr_kernel<1>, dim3((unsigned)grid), dim3(256), 0, st, rowptr, col, val, x, N, H, V, E, out);
+    const bool vec4 = (H % 4 == 0) && ps_aligned16({x, out});
+    PS_LAUNCH_VEC(spmm_csr_kernel<VEC>, vec4, dim3((unsigned)grid), dim3(256), st, rowptr, col, val, x, N, H, V, E, out);
     PS_CHECK_LAUNCH();
     return PS_OK;
 }

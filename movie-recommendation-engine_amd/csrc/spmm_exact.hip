@@ -10,33 +10,13 @@
 // began in an earlier slice, entry 2 w + 1 the piece of the row that begins in slice w and runs on.
 // ps_sddmm_csr walks the same slices; the row of g stays in registers while the CSR row lasts.
 // include/pinsage_hip.h states the arithmetic; tests/helpers/spmm_cases.py restates it bit for bit.
-#include <initializer_list>
 #include "ps_common.h"
+#include "row_sweep.h"
 
 namespace {
 
 constexpr int SLICE = 512;                     // ps_spmm_exact_slice()
 constexpr int UNROLL = 8;
-
-template <int VEC>
-__device__ __forceinline__ void load_vec(const float *__restrict__ p, bool ok, float (&r)[VEC]) {
-    if (VEC == 4) {
-        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (ok) q = *reinterpret_cast<const float4 *>(p);
-        r[0] = q.x; r[1 % VEC] = q.y; r[2 % VEC] = q.z; r[3 % VEC] = q.w;
-    } else {
-        r[0] = ok ? p[0] : 0.f;
-    }
-}
-template <int VEC>
-__device__ __forceinline__ void store_vec(float *__restrict__ p, const float (&r)[VEC]) {
-    if (VEC == 4) *reinterpret_cast<float4 *>(p) = make_float4(r[0], r[1 % VEC], r[2 % VEC], r[3 % VEC]);
-    else p[0] = r[0];
-}
-
-__device__ __forceinline__ float lane_f32(float v, int t) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), t));
-}
 
 // the last row r in [0, V) with rowptr[r] <= e (rowptr[0] = 0 <= e < rowptr[V])
 __device__ __forceinline__ int64_t row_of(const int64_t *__restrict__ rowptr, int64_t V, int64_t e) {
@@ -224,12 +204,6 @@ __global__ __launch_bounds__(256) void sddmm_kernel(const int64_t *__restrict__ 
     }
 }
 
-inline bool aligned16(std::initializer_list<const void *> ps) {
-    size_t m = 0;
-    for (const void *p : ps) m |= reinterpret_cast<size_t>(p);
-    return m % 16 == 0;
-}
-
 inline size_t exact_bytes(int64_t E, int H) { return 256 + ps_align256((size_t)(2 * ps_cdiv(E, SLICE)) * H * sizeof(float)); }
 
 template <int VEC>
@@ -269,15 +243,13 @@ extern "C" int ps_spmm_csr_exact(const int64_t *rowptr, const int32_t *col, cons
     // the empty rows (no wave visits them) are the zeros of this fill; every other row is stored once by one of the launches
     if (ps_fill_async(out, 0, (size_t)V * H * sizeof(float), st) != hipSuccess) return PS_ELAUNCH;
     float *part = reinterpret_cast<float *>(ps_ws_base(workspace));
-    const bool vec4 = (H % 4 == 0) && aligned16({x, out});
-    if (vec4) {
-        hipLaunchKernelGGL(spmm_exact_kernel<4>, dim3((unsigned)grid), dim3(256), 0, st, rowptr, col, val, x, N, H, V, E, out, part);
-        if (waves > 1) hipLaunchKernelGGL(spmm_exact_combine_kernel<4>, dim3((unsigned)grid), dim3(256), 0, st, rowptr, H, V, E, out, part);
-    } else {
-        hipLaunchKernelGGL(spmm_exact_kernel<1>, dim3((unsigned)grid), dim3(256), 0, st, rowptr, col, val, x, N, H, V, E, out, part);
-        if (waves > 1) hipLaunchKernelGGL(spmm_exact_combine_kernel<1>, dim3((unsigned)grid), dim3(256), 0, st, rowptr, H, V, E, out, part);
-    }
+    const bool vec4 = (H % 4 == 0) && ps_aligned16({x, out});
+    PS_LAUNCH_VEC(spmm_exact_kernel<VEC>, vec4, dim3((unsigned)grid), dim3(256), st, rowptr, col, val, x, N, H, V, E, out, part);
     PS_CHECK_LAUNCH();
+    if (waves > 1) {
+        PS_LAUNCH_VEC(spmm_exact_combine_kernel<VEC>, vec4, dim3((unsigned)grid), dim3(256), st, rowptr, H, V, E, out, part);
+        PS_CHECK_LAUNCH();
+    }
     return PS_OK;
 }
 
@@ -290,7 +262,7 @@ extern "C" int ps_sddmm_csr(const int64_t *rowptr, const int32_t *col, const flo
     const int64_t grid = ps_cdiv(waves, 4);
     if (waves > 0x7fffffff) return PS_EUNSUPPORTED;
     hipStream_t st = ps_stream(stream);
-    if ((H % 4 == 0) && aligned16({x, g})) launch_sddmm<4>((unsigned)grid, st, rowptr, col, x, N, g, V, H, E, d);
+    if ((H % 4 == 0) && ps_aligned16({x, g})) launch_sddmm<4>((unsigned)grid, st, rowptr, col, x, N, g, V, H, E, d);
     else launch_sddmm<1>((unsigned)grid, st, rowptr, col, x, N, g, V, H, E, d);
     PS_CHECK_LAUNCH();
     return PS_OK;

@@ -192,7 +192,7 @@ GATE_CASES = (
 )
 PLANTED = ("over", "huge", "twin", "neg", "negmin", "late", "one")      # the planted rows, the last seven of every gate case
 UNROLL = 8                                  # csrc/neigh_agg.hip
-ROW_GRID_CAP = 256 * 16                     # row_grid(): workgroups of four waves
+ROW_GRID_CAP = 256 * 16                     # ps_row_grid() (csrc/ps_common.h): workgroups of four waves
 
 
 def _cdiv(a, b):

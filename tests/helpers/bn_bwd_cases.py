@@ -38,7 +38,7 @@ from helpers import linear_bwd_cases as lb
 from helpers.spmm_cases import _fma
 
 U32 = 2.0 ** -24
-BN_ROWS, BN_UNROLL = 128, 4                 # csrc/row_norm.h: PS_BN_ROWS; csrc/batch_norm_bwd.hip
+BN_ROWS, BN_UNROLL = 128, 4                 # csrc/col_sums.h: PS_BN_ROWS; csrc/batch_norm_bwd.hip
 KEEP = bc.KEEP                              # ps_bn_apply keeps this many sweeps of a row in registers: where the forward changes path
 EPS = bc.EPS
 FLAGSETS = lb.FLAGSETS                      # (relu, l2norm)

@@ -30,9 +30,9 @@ from fractions import Fraction
 
 import numpy as np
 
-BN_ROWS, BN_UNROLL, KEEP = 128, 8, 4        # csrc/batch_norm.hip
+BN_ROWS, BN_UNROLL, KEEP = 128, 8, 4        # csrc/col_sums.h: PS_BN_ROWS; csrc/batch_norm.hip
 GRID_X_CAP = 65535                          # bn_partial_kernel's grid.x
-ROW_GRID_CAP = 256 * 16                     # row_grid(): workgroups of four waves
+ROW_GRID_CAP = 256 * 16                     # ps_row_grid() (csrc/ps_common.h): workgroups of four waves
 EPS, MOMENTUM = 1e-5, 0.1                   # nn.BatchNorm1d's defaults
 CONST = np.float32(3.703125)
 OUTPUTS = ("mean", "var", "scale", "rm", "rv")
