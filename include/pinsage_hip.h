@@ -417,6 +417,59 @@ int ps_bn_bwd(const float *z, const float *gy, int64_t M, int N, const float *me
               const float *beta, float eps, int flags, float *gz, float *dgamma, float *dbeta, void *workspace,
               size_t workspace_bytes, ps_stream_t stream);
 
+/* ---- a9 (model/aggregators.py): nn.LayerNorm of ImportanceAggregator.forward with the zeroing of rows without neighbours behind it
+ * (reference model/aggregators.py:213-287), both directions, csrc/layer_norm.hip.  Caller-allocated buffers, no allocation, no
+ * synchronisation, no float atomics: every output bit is a function of the inputs, whatever the workspace held before the call.
+ *
+ * ps_layer_norm: F.layer_norm over the last dimension of x float[M,N] (dense rows) with gamma, beta float[N] -> y float[M,N], one
+ *   wave per row, one launch.  VEC = 4 when N % 4 == 0 and x, y, gamma, beta are 16-byte aligned, else 1 (ps_bn_apply's rule).  A
+ *   lane's columns are 64 VEC k + VEC lane + e, sweep k and element e ascending.  All arithmetic is fp32:
+ *     S = the wave sum (the balanced tree of the other row kernels) of the lane chains acc = acc + x_c from +0.0; mean = S / (float)N;
+ *     d_c = x_c - mean (rounded); Q = the wave sum of the lane chains acc = fmaf(d_c, d_c, acc) from +0.0; var = Q / (float)N;
+ *     rstd = 1.0f / sqrtf(var + eps)  (sqrt and division correctly rounded, as ps_bn_bwd's);
+ *     xh_c = d_c * rstd; y_c = fmaf(xh_c, gamma_c, beta_c).
+ *   Two passes, the mean first and then the centred squares, and not E[x^2] - mean^2: a row of 100 +- 0.05 has E[x^2] = 10 000 and
+ *   var = 0.0025, and one fp32 ulp of 10 000 is 0.001 -- the single-pass difference keeps no correct digit of such a variance,
+ *   the centred squares keep all of them.  Rows of up to four sweeps are read once and stay in registers between the passes;
+ *   longer rows are read again; both give the same bits.
+ *   mean, rstd float[M]: both or neither (one alone: PS_EINVAL); ps_layer_norm_bwd reads them.
+ *   live int32[M] or NULL (every row is live): row r is live iff live[r] > 0.  A dead row's x is not read; its y is +0.0 throughout
+ *   and its mean[r] and rstd[r] are +0.0 (the aggregator's zeros for a node without neighbours).  A live row with a NaN is NaN
+ *   throughout.  y may be x: in place gives the bits of out of place.
+ *   PS_OK for M == 0, whatever the pointers; PS_EINVAL for M < 0, N < 1 or (M > 0) a null x, y, gamma or beta; PS_EUNSUPPORTED for
+ *   M > 2^33 - 4 (every row has a wave of its own; grid.x holds 2^31 - 1 workgroups of four).  Nothing is written on an error.
+ *
+ * ps_layer_norm_bwd: the backward of the above for the same x, mean, rstd (ps_layer_norm's outputs), gamma and live; gy float[M,N] is
+ *   the gradient of y.  Outputs: gx float[M,N] or NULL; dgamma, dbeta float[N], both or neither (one alone: PS_EINVAL).  VEC = 4 when
+ *   N % 4 == 0 and x, gy, gx (if given), gamma are 16-byte aligned, else 1.
+ *   Per element, fp32:  d = x - mean[r] (rounded); xh = d * rstd[r] (the forward's bits); gg = gy * gamma_c (rounded).
+ *   Per row, fp32, the lane chains over the columns in the order above:  c1 = the wave sum of acc = acc + gg; c2 = the wave sum of
+ *     acc = fmaf(gg, xh, acc); k1 = c1 / (float)N, k2 = c2 / (float)N;
+ *     gx_c = rstd[r] * fmaf(-xh, k2, gg - k1)  (the difference rounded, then the fmaf, then the product: ps_bn_bwd's form transposed).
+ *   A dead row: gx is +0.0, neither x nor gy is read, and the row adds nothing to the columns.
+ *   Per column, fp64, over the live rows:  S1 = sum_r (double)gy, S2 = sum_r (double)gy * (double)xh (the product of two fp32 values
+ *     is exact), in ps_bn_batch_stats' summation order: partitions of 128 consecutive rows of M (counted over all rows, dead or
+ *     alive), within a partition four strided row subsets (r0 + w, r0 + w + 4, ...) summed sequentially and added as
+ *     ((s0 + s1) + s2) + s3, the partitions added ascending from 0.0.  dbeta = (float)S1, dgamma = (float)S2.
+ *   Rows in fp32, columns in fp64: a row's sums run over N terms (a few hundred) as 64 short chains and a tree, so their error is a
+ *   few ulps of sum |term|; a column's run over M terms -- tens of thousands, of either sign -- where an fp32 chain would lose
+ *   M 2^-24 of sum |term| against a result that cancellation makes much smaller.  The fp64 sums (exact products included) leave the
+ *   one rounding to fp32 at the end.
+ *   gx may be gy: the column sums are launched before the rows, and a lane reads gy[c] for the last time before it writes gx[c].
+ *   Three launches: the partitions' column sums, their sum, gx; the first two only with dgamma / dbeta, the last only with gx.  With
+ *   all three outputs NULL: PS_OK, nothing written.  M == 0: PS_OK, and dgamma / dbeta, if given, are set to zeros.
+ *   workspace: ps_layer_norm_bwd_workspace_bytes(M, N) bytes -- 16 N bytes per partition, a function of (M, N) only, 0 for M < 1 or
+ *   N < 1 -- 8-byte aligned, not preserved between calls; it may be NULL when dgamma is NULL.
+ *   PS_EINVAL for M < 0, N < 1, (M > 0) a null x, gy, mean, rstd or gamma, and with dgamma a null workspace or one that is not 8-byte
+ *   aligned; PS_EWORKSPACE for a short one; PS_EUNSUPPORTED for M > 2^33 - 4 or more than 65 535 column blocks (N > 65 535 * 64 VEC).
+ *   Nothing is written in any of these cases. */
+int ps_layer_norm(const float *x, int64_t M, int N, const float *gamma, const float *beta, float eps, const int32_t *live, float *y,
+                  float *mean, float *rstd, ps_stream_t stream);
+size_t ps_layer_norm_bwd_workspace_bytes(int64_t M, int N);
+int ps_layer_norm_bwd(const float *x, const float *gy, int64_t M, int N, const float *mean, const float *rstd, const float *gamma,
+                      const int32_t *live, float *gx, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes,
+                      ps_stream_t stream);
+
 /* One layer of the pooled branch in one call: y = epilogue( x W^T + pool(h_full) W2^T + b ), where pool(h_full) is
  * ps_importance_pool(h_full, n_full, H, ids, counts, wts, nvalid, M, T, max_idx, renorm) and the rest is ps_linear with
  * x2 = that pooled matrix (K2 = H): the same bits as that pair.  Rows that keep no neighbour skip the K2 half (their pooled row is

@@ -1,4 +1,5 @@
-// Two fp64 sums per column of an [M, N] matrix without atomics (ps_bn_batch_stats: z and z^2; ps_bn_bwd: ga and ga xh).
+// Two fp64 sums per column of an [M, N] matrix without atomics (ps_bn_batch_stats: z and z^2; ps_bn_bwd: ga and ga xh;
+// ps_layer_norm_bwd: gy and gy xh over the live rows, a dead row inside its partition adding (+0.0, +0.0)).
 // The rows are cut into partitions of PS_BN_ROWS consecutive rows (a function of M only).  ps_col_sums_partition is one
 // workgroup's work on partition p and its 64 VEC columns: wave w takes the rows r0 + w, r0 + w + 4, ... ascending, every lane
 // adds its columns' two addends in fp64, and the four waves' sums are added in wave order through LDS into part[p, 0 / 1, col].

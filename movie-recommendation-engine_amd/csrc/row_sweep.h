@@ -1,7 +1,8 @@
 // What the one-wave-per-row kernels share: the 16-byte / 4-byte sweeps of a row (VEC = 4 / 1 floats per lane), the kept id of a
 // neighbour slot and a lane's value for the whole wave (the gathers of neigh_agg*.hip, spmm_exact.hip), and for the kernels that
 // divide a row by its norm (ps_bn_apply, ps_linear_epilogue_bwd, ps_bn_bwd) the clamped norm of F.normalize, the batch-norm
-// pre-activation and the epilogue's backward.
+// pre-activation and the epilogue's backward; for the layer norm (layer_norm.hip) a row's mean and rstd, its xh and the two
+// row sums of its backward.
 // A lane's sum of squares is its own fmaf chain over its columns 64 VEC k + VEC lane + e (sweep k and element e ascending);
 // ps_row_norm turns the 64 chains into the norm.
 #pragma once
@@ -113,4 +114,114 @@ __device__ __forceinline__ float ps_epilogue_ga(float t, float g, bool relu, boo
     float gt = g;
     if (l2) gt = below ? g / c : fmaf(-(t / c), s, g) / c;
     return (relu && !(t > 0.f)) ? 0.f : gt;
+}
+
+// ---- layer norm over a row (csrc/layer_norm.hip) ----
+// Rows of up to PS_LN_KEEP sweeps stay in registers between the passes over them; the sweeps beyond are read again, by the lane
+// that read them before (and that writes the same addresses afterwards: the output may be the input).  Both forms run the same
+// chains in the same order and give the same bits.
+constexpr int PS_LN_KEEP = 4;
+
+// xh of one element: the difference rounded, then the product
+__device__ __forceinline__ float ps_ln_xhat(float x, float mean, float rstd) { return (x - mean) * rstd; }
+
+// (mean, rstd) of the row xr[0..N), in every lane, two passes: S = the wave sum of the lane chains acc = acc + x from +0.0,
+// mean = S / (float)N, Q = the wave sum of the chains acc = fmaf(d, d, acc) of d = x - mean, rstd = 1 / sqrtf(Q / (float)N + eps).
+// kept[k] receives the lane's share of sweep k < PS_LN_KEEP (+0.0 past N).  A column past N adds +0.0 to S and nothing to Q.
+template <int VEC>
+__device__ __forceinline__ float2 ps_ln_row_stats(const float *xr, int N, float eps, float (&kept)[PS_LN_KEEP][VEC]) {
+    const int lane = threadIdx.x & 63;
+    const int chunk = 64 * VEC;
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < PS_LN_KEEP; ++k) {
+        const int col = k * chunk + lane * VEC;
+        load_vec<VEC>(xr + col, col < N, kept[k]);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc = acc + kept[k][e];
+    }
+    for (int c0 = PS_LN_KEEP * chunk; c0 < N; c0 += chunk) {
+        const int col = c0 + lane * VEC;
+        float xx[VEC];
+        load_vec<VEC>(xr + col, col < N, xx);
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) acc = acc + xx[e];
+    }
+    const float mean = ps_wave_sum_f32(acc) / (float)N;
+    acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < PS_LN_KEEP; ++k) {
+        if (k * chunk + lane * VEC < N) {
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const float d = kept[k][e] - mean;
+                acc = fmaf(d, d, acc);
+            }
+        }
+    }
+    for (int c0 = PS_LN_KEEP * chunk; c0 < N; c0 += chunk) {
+        const int col = c0 + lane * VEC;
+        if (col < N) {
+            float xx[VEC];
+            load_vec<VEC>(xr + col, true, xx);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                const float d = xx[e] - mean;
+                acc = fmaf(d, d, acc);
+            }
+        }
+    }
+    const float var = ps_wave_sum_f32(acc) / (float)N;
+    return make_float2(mean, 1.0f / sqrtf(var + eps));
+}
+
+// the VEC elements at column col < N of the layer norm's backward: gg = gy * gamma (rounded) and xh
+template <int VEC>
+__device__ __forceinline__ void ps_ln_bwd_elems(const float *xr, const float *gr, const float *__restrict__ gamma, int col,
+                                                float mean, float rstd, float (&gg)[VEC], float (&xh)[VEC]) {
+    float xx[VEC], g[VEC], ga[VEC];
+    load_vec<VEC>(xr + col, true, xx);
+    load_vec<VEC>(gr + col, true, g);
+    load_vec<VEC>(gamma + col, true, ga);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+        gg[e] = g[e] * ga[e];
+        xh[e] = ps_ln_xhat(xx[e], mean, rstd);
+    }
+}
+
+// (c1, c2) of a row of the layer norm's backward, in every lane: the wave sums of the lane chains acc = acc + gg and
+// acc = fmaf(gg, xh, acc) from +0.0.  gg[k] / xh[k] receive the lane's share of sweep k < PS_LN_KEEP (untouched past N).
+template <int VEC>
+__device__ __forceinline__ float2 ps_ln_bwd_row_sums(const float *xr, const float *gr, const float *__restrict__ gamma, int N,
+                                                     float mean, float rstd, float (&gg)[PS_LN_KEEP][VEC],
+                                                     float (&xh)[PS_LN_KEEP][VEC]) {
+    const int lane = threadIdx.x & 63;
+    const int chunk = 64 * VEC;
+    float a1 = 0.f, a2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < PS_LN_KEEP; ++k) {
+        const int col = k * chunk + lane * VEC;
+        if (col < N) {
+            ps_ln_bwd_elems<VEC>(xr, gr, gamma, col, mean, rstd, gg[k], xh[k]);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                a1 = a1 + gg[k][e];
+                a2 = fmaf(gg[k][e], xh[k][e], a2);
+            }
+        }
+    }
+    for (int c0 = PS_LN_KEEP * chunk; c0 < N; c0 += chunk) {
+        const int col = c0 + lane * VEC;
+        if (col < N) {
+            float g1[VEC], x1[VEC];
+            ps_ln_bwd_elems<VEC>(xr, gr, gamma, col, mean, rstd, g1, x1);
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) {
+                a1 = a1 + g1[e];
+                a2 = fmaf(g1[e], x1[e], a2);
+            }
+        }
+    }
+    return make_float2(ps_wave_sum_f32(a1), ps_wave_sum_f32(a2));
 }

@@ -8,6 +8,9 @@ ps_attention_weights + ps_importance_pool and ps_linear + ps_gather_max for CUDA
 built); under autograd the linears are F.linear on the tape and the gather stage is sampling.attention / sampling.max_pool, whose
 backward is the transposed gathers of csrc/neigh_agg_bwd.hip (sampling.grad_method = "torch" restores the torch code there).
 CPU tensors and other dtypes keep the batched torch code (`_forward_torch`).
+ImportanceAggregator's Linear and LayerNorm behind the pooling are a switch: `ImportanceAggregator.norm_method = "hip"` (class or
+instance; the default is "torch") runs dense.linear and dense.layer_norm -- ps_layer_norm, with the rows without neighbours as its
+mask -- in both directions.
 """
 from __future__ import annotations
 
@@ -223,9 +226,30 @@ class ImportanceAggregator(nn.Module):
         self.transform = nn.Linear(in_channels, out_channels)
         self.norm = nn.LayerNorm(out_channels)
 
+    # how the Linear and the LayerNorm behind the pooling are computed: "torch" (the default) keeps F.linear on the tape and
+    # F.layer_norm + torch.where in both directions; "hip" runs dense.linear and dense.layer_norm (ps_layer_norm with the rows
+    # without neighbours as its `live` mask; on the tape, under sampling.grad_method == "hip", their HIP backwards).  Set on the
+    # class or on an instance.
+    norm_method = "torch"
+
+    def _hip_norm(self, features):
+        """does this call take the kernel path?"""
+        if self.norm_method not in ("hip", "torch"):
+            raise ValueError(f"ImportanceAggregator.norm_method must be 'hip' or 'torch', not {self.norm_method!r}")
+        n = self.norm
+        return (self.norm_method == "hip" and _cuda_fp32(features) and features.dim() == 2 and type(n) is nn.LayerNorm
+                and n.elementwise_affine and n.bias is not None and tuple(n.normalized_shape) == (self.transform.out_features,)
+                and all(p.dtype == torch.float32 and p.device == features.device for p in self.parameters()))
+
     def forward(self, features, neighbors, importance_weights):
+        hip = self._hip_norm(features)
         ids, w, nvalid = _pad(neighbors, int(features.size(0)), importance_weights)
         pooled = _pool(features, ids, w, nvalid)
+        if hip:
+            # dense.linear and dense.layer_norm route themselves: off the tape one kernel each, on it LinearFn / LayerNormFn
+            t = dense.linear(pooled, self.transform.weight, self.transform.bias)
+            return dense.layer_norm(t, self.norm.weight, self.norm.bias, self.norm.eps,
+                                    live=torch.from_numpy(nvalid).to(t.device))
         if torch.is_grad_enabled() and (pooled.requires_grad or any(p.requires_grad for p in self.parameters())):
             t = F.linear(pooled, self.transform.weight.to(pooled.device), self.transform.bias.to(pooled.device))
         else:

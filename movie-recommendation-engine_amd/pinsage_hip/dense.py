@@ -390,6 +390,123 @@ class BatchNormFn(torch.autograd.Function):
         return gz, dgamma if need[1] else None, dbeta if need[2] else None, None, None, None, None, None, None
 
 
+def _live_vec(live, m, device):
+    if live is None:
+        return None
+    if live.dtype != torch.int32 or live.dim() != 1 or live.numel() != m or live.device != device:
+        raise ValueError(f"live must be an int32 [{m}] vector on the device of x")
+    return live.contiguous()
+
+
+def layer_norm_fwd(x, gamma, beta, eps, live=None, out=None, stats=True):
+    """(y [M, N], mean [M], rstd [M]) of F.layer_norm over the last dimension of x [M, N] (ps_layer_norm): one wave per row, two
+    passes in fp32 (the mean, then the centred squares).  live: int32 [M] or None; a row with live <= 0 is not read and gives
+    zeros (y, mean and rstd).  stats=False: mean and rstd are None and not written.  out: a contiguous fp32 [M, N] device tensor
+    to write into; out=x works in place and gives the bits of a new tensor."""
+    _require_cuda(x, gamma, beta, live, out)
+    if x.dtype != torch.float32:
+        raise TypeError("fp32 expected")
+    if x.dim() != 2:
+        raise ValueError("2-D matrix expected")
+    if out is None or out is not x:
+        x = x.contiguous()
+    elif not x.is_contiguous():
+        raise ValueError("in place: x must be contiguous")
+    M, N = x.size(0), x.size(1)
+    gamma, beta = (_fp32_vec(n, t, N, x.device) for n, t in (("gamma", gamma), ("beta", beta)))
+    live = _live_vec(live, M, x.device)
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (M, N) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("out must be a contiguous fp32 [M, N] tensor on the device of x")
+    mean = rstd = None
+    if stats:
+        mean, rstd = (torch.empty(M, dtype=torch.float32, device=x.device) for _ in range(2))
+    with torch.cuda.device(x.device):
+        nv.call("ps_layer_norm", nv.ptr(x), M, N, nv.ptr(gamma), nv.ptr(beta), float(eps), nv.ptr(live), nv.ptr(out), nv.ptr(mean),
+                nv.ptr(rstd), nv.stream())
+    return out, mean, rstd
+
+
+def layer_norm_bwd(x, gy, mean, rstd, gamma, live=None, need_gx=True, need_affine=True, out=None):
+    """(gx [M, N], dgamma [N], dbeta [N]) of layer_norm_fwd for the same x, mean, rstd, gamma and live (ps_layer_norm_bwd).  xh is
+    recomputed from x with the forward's bits; the column sums are fp64 in a fixed order; the workspace comes from torch's
+    allocator.  need_gx / need_affine False: that output is None and not computed.  out: a contiguous fp32 [M, N] device tensor
+    for gx; out=gy works in place."""
+    _require_cuda(x, gy, mean, rstd, gamma, live, out)
+    if x.dtype != torch.float32 or gy.dtype != torch.float32:
+        raise TypeError("fp32 expected")
+    if x.dim() != 2 or x.shape != gy.shape:
+        raise ValueError(f"shape mismatch: x {tuple(x.shape)} vs gy {tuple(gy.shape)}")
+    x = x.contiguous()
+    M, N = x.size(0), x.size(1)
+    gamma = _fp32_vec("gamma", gamma, N, x.device)
+    mean, rstd = (_fp32_vec(n, t, M, x.device) for n, t in (("mean", mean), ("rstd", rstd)))
+    live = _live_vec(live, M, x.device)
+    gx = dgamma = dbeta = None
+    if out is None:
+        gy = gy.contiguous()
+        if need_gx:
+            gx = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (M, N) or not out.is_contiguous() or not gy.is_contiguous() \
+            or out.device != x.device:
+        raise ValueError("out must be a contiguous fp32 [M, N] tensor on the device of x (and gy contiguous)")
+    elif need_gx:
+        gx = out
+    ws, wsb = None, 0
+    if need_affine:
+        dgamma, dbeta = (torch.empty(N, dtype=torch.float32, device=x.device) for _ in range(2))
+        ws, wsb = nv.workspace("ps_layer_norm_bwd_workspace_bytes", x.device, M, N)
+    with torch.cuda.device(x.device):
+        nv.call("ps_layer_norm_bwd", nv.ptr(x), nv.ptr(gy), M, N, nv.ptr(mean), nv.ptr(rstd), nv.ptr(gamma), nv.ptr(live), nv.ptr(gx),
+                nv.ptr(dgamma), nv.ptr(dbeta), nv.ptr(ws), wsb, nv.stream())
+    return gx, dgamma, dbeta
+
+
+def layer_norm_torch(x, gamma, beta, eps=1e-5, live=None):
+    """layer_norm() as a differentiable torch expression (grad_method "torch", other dtypes, CPU tensors)"""
+    y = F.layer_norm(x, (x.size(-1),), gamma, beta, eps)
+    if live is None:
+        return y
+    return torch.where((live > 0).unsqueeze(-1), y, torch.zeros_like(y))
+
+
+def layer_norm(x, gamma, beta, eps=1e-5, live=None):
+    """F.layer_norm over the last dimension of x [M, N], zeros in the rows whose `live` (int32 [M], optional) is not positive.
+    Off the tape: one ps_layer_norm into a new tensor, without statistics.  With autograd on and x, gamma or beta requiring a
+    gradient the call stays on the tape: LayerNormFn (the same kernel forward, ps_layer_norm_bwd backward) for CUDA fp32 operands
+    under sampling.grad_method == "hip", layer_norm_torch elsewhere ("torch", other dtypes, CPU tensors; a backward that is itself
+    to be differentiated needs "torch" too: LayerNormFn is once-differentiable)."""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, gamma, beta)):
+        from .graph import use_hip_grad
+        if x.dim() == 2 and use_hip_grad(x, gamma, beta) and (live is None or live.is_cuda):
+            return LayerNormFn.apply(x, gamma, beta, float(eps), live)
+        return layer_norm_torch(x, gamma, beta, eps, live)
+    return layer_norm_fwd(x, gamma, beta, eps, live, stats=False)[0]
+
+
+class LayerNormFn(torch.autograd.Function):
+    """Differentiable layer_norm() for CUDA fp32 operands.  Forward: ps_layer_norm with its statistics -- the inference call's
+    bits.  Saved: x, mean, rstd, gamma and live; neither xh nor y.  Backward: one ps_layer_norm_bwd -- gx only if x needs it,
+    dgamma / dbeta only if gamma or beta does.  No float atomics, nothing waits for the host: the same bits on every run."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, live):
+        x = x.contiguous()
+        y, mean, rstd = layer_norm_fwd(x, gamma, beta, eps, live)
+        ctx.save_for_backward(x, mean, rstd, gamma, live)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, mean, rstd, gamma, live = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gy = gy.contiguous()                                          # y.sum().backward() hands over a stride-0 tensor
+        gx, dgamma, dbeta = layer_norm_bwd(x, gy, mean, rstd, gamma, live, need_gx=need[0], need_affine=need[1] or need[2])
+        return gx, dgamma if need[1] else None, dbeta if need[2] else None, None, None
+
+
 GCN_MIN_ROWS, GCN_MAX_T = 64 * 384, 16     # the M / T gates of ps_gcn_layer: gcn_orders makes no order the layer call would refuse
 
 

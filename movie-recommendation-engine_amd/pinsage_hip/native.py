@@ -78,6 +78,9 @@ PROTOTYPES = {
     "ps_bn_apply": "i pqipppipp",
     "ps_bn_bwd_workspace_bytes": "z qi",
     "ps_bn_bwd": "i ppqippppfippppzp",
+    "ps_layer_norm": "i pqippfppppp",
+    "ps_layer_norm_bwd_workspace_bytes": "z qi",
+    "ps_layer_norm_bwd": "i ppqippppppppzp",
     "ps_permute_k": "i pqiipp",
     "ps_linear": "i pqipipipipiipp",
     "ps_linear_wgrad_partition": "q q",
