@@ -339,7 +339,15 @@ int ps_bn_apply(const float *z, int64_t M, int N, const float *mean, const float
  * x2/W2 eliminate torch.cat([h_self, h_neigh]) (:238): W = lin_update.weight[:, :H], W2 = [:, H:]
  * (ldw / ldw2 = row strides of W / W2 in floats).  flags: PS_RELU, PS_L2NORM (F.normalize, eps 1e-12), PS_WPERM: W (and W2)
  * are stored in the order the kernel stages them (ps_permute_k; needs 16-byte aligned operands and K % 32 == 0, else PS_EINVAL):
- * same results bit for bit, 32 fewer vector instructions per 64 MFMAs -- for weights that are multiplied many times. */
+ * same results bit for bit, 32 fewer vector instructions per 64 MFMAs -- for weights that are multiplied many times.
+ * Per output, fp32: acc = fmaf(x[m,k], W[n,k], acc) over k ascending from +0.0, then the same over x2 / W2; each of the two chains
+ * runs on to a multiple of 32 k over terms +0.0 * +0.0 (which turn an accumulator of -0.0 into +0.0 and change nothing else);
+ * t = acc + b[n], or acc + 0.0f when b is NULL.  NaN and infinities follow IEEE 754 through the chain: a NaN or Inf - Inf
+ * anywhere in it is a NaN output.
+ * PS_RELU: t > 0 or t is NaN ? t : +0.0 (so -0.0 gives +0.0, unlike ps_bn_apply).
+ * PS_L2NORM: the row divided by nrm = sqrtf(sum_n t^2), 1e-12f where nrm < 1e-12f -- a NaN norm stays, so a row with a NaN is NaN
+ * throughout, as F.normalize's clamp_min leaves it; an infinite norm gives Inf / Inf = NaN and +-0.0 for the finite columns.  The
+ * quotient is the correctly rounded t / nrm. */
 #define PS_RELU 1
 #define PS_L2NORM 2
 #define PS_WPERM 4
@@ -473,7 +481,9 @@ int ps_layer_norm_bwd(const float *x, const float *gy, int64_t M, int N, const f
 /* One layer of the pooled branch in one call: y = epilogue( x W^T + pool(h_full) W2^T + b ), where pool(h_full) is
  * ps_importance_pool(h_full, n_full, H, ids, counts, wts, nvalid, M, T, max_idx, renorm) and the rest is ps_linear with
  * x2 = that pooled matrix (K2 = H): the same bits as that pair.  Rows that keep no neighbour skip the K2 half (their pooled row is
- * +0.0); the pooled rows are never written as a matrix.  Served: N == 256, flags PS_RELU | PS_L2NORM (PS_WPERM allowed),
+ * +0.0, and +0.0 * w changes no accumulator for finite w -- precondition: W2 is finite; a NaN or infinite W2 poisons such rows in
+ * the pair and not here; NaN and infinities in x, h_full, W and b are carried as ps_linear carries them); the pooled rows are
+ * never written as a matrix.  Served: N == 256, flags PS_RELU | PS_L2NORM (PS_WPERM allowed),
  * M >= 24 576, T <= 16, 16-byte aligned operands with K % 32 == 0 and H % 32 == 0; any other call returns PS_EUNSUPPORTED
  * without doing anything, and so does every call under the environment switch PS_GCN_FUSED=0 -- the caller then runs the pair.
  * workspace: ps_gcn_layer_workspace_bytes(M, H) bytes, 16-byte aligned, not preserved between calls.

@@ -420,7 +420,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, f32x16 (&acc)[T
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 float v = acc[a][b][r] + bv;
-                if (relu) v = v > 0.f ? v : 0.f;
+                if (relu) v = !(v <= 0.f) ? v : 0.f;                   // a NaN stays, as torch's relu keeps it; -0.0 gives +0.0
                 if (col >= g.N) v = 0.f;
                 acc[a][b][r] = v;
             }
@@ -453,7 +453,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs &g, f32x16 (&acc)[T
 #pragma unroll
             for (int w = 0; w < WN; ++w) t += sRed[row * WN + w];
             float nrm = sqrtf(t);
-            nrm = nrm > 1e-12f ? nrm : 1e-12f;
+            nrm = nrm < 1e-12f ? 1e-12f : nrm;                      // ps_row_clamp's form: a NaN norm stays, the row is x / NaN
             const bool tame = nrm >= 0x1p-40f && nrm <= 0x1p40f;
             *reinterpret_cast<f32x4 *>(sNrm + row * 4) = f32x4{nrm, 1.0f / nrm, nrm * 0x1p-60f, tame ? 0.f : 1.f};
         }
@@ -912,7 +912,7 @@ __global__ __launch_bounds__(DMA_WAVES * 64, 2) void gemm_dma_kernel(GemmArgs g)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 float v = acc[a][b][r] + bias;
-                if (relu) v = v > 0.f ? v : 0.f;
+                if (relu) v = !(v <= 0.f) ? v : 0.f;                   // a NaN stays, as torch's relu keeps it; -0.0 gives +0.0
                 if (col >= g.N) v = 0.f;
                 acc[a][b][r] = v;
             }
@@ -941,7 +941,7 @@ __global__ __launch_bounds__(DMA_WAVES * 64, 2) void gemm_dma_kernel(GemmArgs g)
 #pragma unroll
                 for (int w = 0; w < 4; ++w) ss += sRed[rowl * 4 + w];
                 float nrm = sqrtf(ss);
-                nrm = nrm > 1e-12f ? nrm : 1e-12f;
+                nrm = nrm < 1e-12f ? 1e-12f : nrm;                      // ps_row_clamp's form: a NaN norm stays, the row is x / NaN
 #pragma unroll
                 for (int b = 0; b < 2; ++b) acc[a][b][r] = acc[a][b][r] / nrm;
             }
@@ -1158,7 +1158,7 @@ __global__ void l2norm_rows_kernel(float *y, int64_t M, int N) {   // N > 256 on
         for (int n = lane; n < N; n += 64) ss = fmaf(y[m * N + n], y[m * N + n], ss);
         ss = ps_wave_sum_f32(ss);
         float nrm = sqrtf(ss);
-        nrm = nrm > 1e-12f ? nrm : 1e-12f;
+        nrm = nrm < 1e-12f ? 1e-12f : nrm;                      // ps_row_clamp's form: a NaN norm stays, the row is x / NaN
         for (int n = lane; n < N; n += 64) y[m * N + n] = y[m * N + n] / nrm;
     }
 }

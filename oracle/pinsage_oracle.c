@@ -352,7 +352,9 @@ int orc_importance_pool_ex(const float *x, int64_t N, int H, const int32_t *ids,
 }
 
 /* ---------- dense: y = act(x W^T + b), optional row L2 normalise (F.normalize eps 1e-12) --
- * k-ordered fp32 fma chain from 0, bias added last (what the MFMA kernel computes).  */
+ * k-ordered fp32 fma chain from 0, bias added last (what the MFMA kernel computes), in the words of include/pinsage_hip.h:
+ * each operand pair's chain runs on to a multiple of 32 k over terms +0.0 * +0.0 (an accumulator of -0.0 becomes +0.0, nothing
+ * else changes); + b[n], or + 0.0f without a bias; PS_RELU t > 0 or t is NaN ? t : +0.0; the clamp keeps a NaN norm.  */
 int orc_linear(const float *x, const float *W, const float *b, int64_t M, int K, int N,
                const float *x2, const float *W2, int K2, int relu, int l2norm, float *y, int threads) {
 #ifdef _OPENMP
@@ -363,9 +365,13 @@ int orc_linear(const float *x, const float *W, const float *b, int64_t M, int K,
         for (int n = 0; n < N; n++) {
             float acc = 0.f;
             for (int k = 0; k < K; k++) acc = fmaf(x[m * K + k], W[(int64_t)n * K + k], acc);
-            if (x2) for (int k = 0; k < K2; k++) acc = fmaf(x2[m * K2 + k], W2[(int64_t)n * K2 + k], acc);
-            if (b) acc += b[n];
-            if (relu && acc < 0.f) acc = 0.f;
+            if (K % 32) acc = fmaf(0.f, 0.f, acc);
+            if (x2) {
+                for (int k = 0; k < K2; k++) acc = fmaf(x2[m * K2 + k], W2[(int64_t)n * K2 + k], acc);
+                if (K2 % 32) acc = fmaf(0.f, 0.f, acc);
+            }
+            acc += b ? b[n] : 0.f;
+            if (relu && acc <= 0.f) acc = 0.f;                      /* -0.0 gives +0.0; a NaN stays */
             o[n] = acc;
         }
         if (l2norm) {
