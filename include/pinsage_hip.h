@@ -607,6 +607,26 @@ int ps_row_dot(const float *A, int64_t nA, const float *B, int64_t nB, int D, co
 int ps_rank_count(const float *E, int64_t N, int D, int64_t id_offset, const float *Q, int64_t nq, const float *thr,
                   const int64_t *tid, int64_t *count, ps_stream_t stream);
 
+/* ---- two-level retrieval: exact re-rank of a first-level search's candidates -------------------------------------------------
+ * The "efficient two-level retrieval" that the reference's approximate index describes (utils/nearest_neighbors.py:70-86: it
+ * stores a candidates_factor and never uses it), scored as its exact search scores (inference.py:120-127): a first-level search
+ * (ps_hamming_topk over LSH codes) returns R = factor * k candidate ids per query, ps_rerank_topk orders them by the exact inner
+ * product.
+ *   E float[N,D]: rows with the ids id_offset .. id_offset + N - 1 (as ps_hamming_topk(id_offset) emits them); Q float[nq,D];
+ *   cand int64[nq,R]: one candidate list per query, as the first-level searches write it.  A candidate is valid iff
+ *   0 <= id - id_offset < N; every other entry (-1 pads, ids beyond the table, negative ids) is skipped and nothing is read
+ *   for it.  An id that occurs several times in a row counts once.
+ *   sim = Q_i . E[id - id_offset] with ps_row_dot's arithmetic (one fmaf chain, columns ascending, from +0.0): bit-identical
+ *   to the ps_linear / ps_dot_topk entry of the pair (a chain that ends in -0.0 -- every product negative and underflowing --
+ *   is reported as +0.0, as the GEMM's bias addition leaves it there).
+ *   vals float[nq,k], ids int64[nq,k]: the k best of the row's distinct valid candidates in ps_dot_topk's order (similarity
+ *   descending by the key of its float bits, ties by ascending id), padded with (-inf, -1).
+ *   k >= 1, D >= 1 (else PS_EINVAL); N < 2^31 and 1 <= R <= ps_rerank_max_candidates() (>= 4096; else PS_EUNSUPPORTED).
+ *   One launch, no workspace: a query's candidate keys stay in LDS (csrc/rerank.hip). */
+int ps_rerank_max_candidates(void);
+int ps_rerank_topk(const float *E, int64_t N, int D, int64_t id_offset, const float *Q, int64_t nq, const int64_t *cand, int R,
+                   int k, float *vals, int64_t *ids, ps_stream_t stream);
+
 /* ---- next row: exact L2 / IVF search behind WeakANDIndex and benchmark_search_methods
  * (utils/nearest_neighbors.py:70-139, 176: faiss.IndexFlatL2 / faiss.IndexIVFFlat).
  * dist(q, x) = |q|^2 + |x|^2 - 2 q.x in fp32; k smallest by (distance, id), ascending; dist float[nq,k]

@@ -1597,20 +1597,7 @@ __global__ void row_dot_kernel(const float *__restrict__ A, int64_t nA, const fl
             out[i] = __builtin_nanf("");
             continue;
         }
-        const float *x = A + a * D, *y = B + b * D;
-        float s = 0.f;
-        if (vec) {
-            for (int k = 0; k < D; k += 4) {
-                const float4 u = *reinterpret_cast<const float4 *>(x + k), v = *reinterpret_cast<const float4 *>(y + k);
-                s = fmaf(u.x, v.x, s);
-                s = fmaf(u.y, v.y, s);
-                s = fmaf(u.z, v.z, s);
-                s = fmaf(u.w, v.w, s);
-            }
-        } else {
-            for (int k = 0; k < D; ++k) s = fmaf(x[k], y[k], s);
-        }
-        out[i] = s;
+        out[i] = ps_fma_chain(A + a * D, B + b * D, D, vec, 0.f);
     }
 }
 

@@ -74,11 +74,7 @@ struct WaveSelect {
 // The sweeps around a WaveSelect, for one row and one wave.  A sweep selects at most kcap keys; k > kcap takes further sweeps,
 // each admitting only keys AFTER the last one emitted -- keys are unique (id in the low word), so the sweeps partition the
 // order exactly.  DESC: largest value first (else smallest); `scan(sel)` offers every candidate of the row once, as
-// topk_key<DESC>(value, id).  Slots beyond the candidates are padding: (-inf or FLT_MAX, -1).
-template <bool DESC>
-__device__ __forceinline__ uint64_t topk_key(float v, uint32_t id) {
-    return ((uint64_t)(DESC ? ~ps_float_order(v) : ps_float_order(v)) << 32) | id;
-}
+// ps_topk_key<DESC>(value, id) (csrc/ps_select.h).  Slots beyond the candidates are padding: (-inf or FLT_MAX, -1).
 template <bool DESC, typename Scan>
 __device__ __forceinline__ void topk_sweeps(uint64_t *queue, int lane, int k, int kcap, float *__restrict__ vals,
                                             int64_t *__restrict__ ids, Scan scan) {
@@ -140,7 +136,7 @@ __global__ __launch_bounds__(256) void row_topk_kernel(const float *__restrict__
                     v = (qnr + xv[u]) - 2.f * v;
                 }
                 if (j == self) v = -INFINITY;
-                sel.offer(ok, topk_key<MODE == 0>(v, (uint32_t)j));
+                sel.offer(ok, ps_topk_key<MODE == 0>(v, (uint32_t)j));
             }
         }
     });
@@ -360,7 +356,7 @@ __global__ __launch_bounds__(256) void ivf_row_topk_kernel(const float *__restri
     #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const float v = (qnr + xv[buf][u]) - 2.f * sv[buf][u];
-                    sel.offer(iv[buf][u] >= 0, topk_key<false>(v, (uint32_t)iv[buf][u]));
+                    sel.offer(iv[buf][u] >= 0, ps_topk_key<false>(v, (uint32_t)iv[buf][u]));
                 }
             };
             skip_empty();

@@ -13,21 +13,9 @@
 
 namespace {
 
-// acc = fmaf(x[k], y[k], acc), k ascending from +0.0: row_dot_kernel's chain (csrc/dense_mfma.hip)
+// acc = fmaf(x[k], y[k], acc), k ascending from +0.0: row_dot_kernel's chain (csrc/ps_common.h)
 __device__ __forceinline__ float chain_dot(const float *__restrict__ x, const float *__restrict__ y, int D, bool vec) {
-    float s = 0.f;
-    if (vec) {
-        for (int k = 0; k < D; k += 4) {
-            const float4 u = *reinterpret_cast<const float4 *>(x + k), v = *reinterpret_cast<const float4 *>(y + k);
-            s = fmaf(u.x, v.x, s);
-            s = fmaf(u.y, v.y, s);
-            s = fmaf(u.z, v.z, s);
-            s = fmaf(u.w, v.w, s);
-        }
-    } else {
-        for (int k = 0; k < D; ++k) s = fmaf(x[k], y[k], s);
-    }
-    return s;
+    return ps_fma_chain(x, y, D, vec, 0.f);
 }
 
 __device__ __forceinline__ bool vec_ok(const float *a, const float *b, int D) {

@@ -139,6 +139,24 @@ int psi_lsh_encode_staged(const float *x, int64_t N, int D, const void *staged, 
 
 __device__ __forceinline__ int ps_lane() { return threadIdx.x & 63; }
 
+// The inner product of ps_linear / ps_dot_topk / ps_row_dot for one pair of rows: acc = fmaf(x[k], y[k], acc), k ascending over
+// n columns, continued from s (+0.0 starts a product).  vec: 16-byte reads -- n % 4 == 0 and both rows 16-byte aligned; the
+// floats, and so the bits, are the same either way.  The rows may lie in global memory or in LDS.
+__device__ __forceinline__ float ps_fma_chain(const float *__restrict__ x, const float *__restrict__ y, int n, bool vec, float s) {
+    if (vec) {
+        for (int k = 0; k < n; k += 4) {
+            const float4 u = *reinterpret_cast<const float4 *>(x + k), v = *reinterpret_cast<const float4 *>(y + k);
+            s = fmaf(u.x, v.x, s);
+            s = fmaf(u.y, v.y, s);
+            s = fmaf(u.z, v.z, s);
+            s = fmaf(u.w, v.w, s);
+        }
+    } else {
+        for (int k = 0; k < n; ++k) s = fmaf(x[k], y[k], s);
+    }
+    return s;
+}
+
 // a / b rounded to nearest, as numpy and python divide.  The instruction sequence the compiler emits for an fp64 `/` is faithful
 // but not always correctly rounded: a quotient within a hair of a rounding midpoint can come out one ulp off (11 of
 // SYN-25M's 50 M CDF entries did).  q is within an ulp of a / b, so the residuals a - q b are exact (fma), and the

@@ -13,6 +13,14 @@ __device__ __forceinline__ float ps_float_unorder(uint32_t u) {
     return __int_as_float(k ^ ((k >> 31) & 0x7fffffff));
 }
 
+// The key of a top-k selection (ps_dot_topk, ps_l2_topk, ps_ivf_topk, ps_rerank_topk): value word << 32 | id, smallest key first.
+// DESC: largest value first (an inner product), else smallest (a distance); equal values by ascending id.  ~0 is no key of a
+// candidate whose id is below 2^32 - 1.
+template <bool DESC>
+__device__ __forceinline__ uint64_t ps_topk_key(float v, uint32_t id) {
+    return ((uint64_t)(DESC ? ~ps_float_order(v) : ps_float_order(v)) << 32) | id;
+}
+
 // (similarity, candidate index) as ONE unsigned word whose integer order is "larger similarity first, then smaller index":
 // high half = the float's place in its total order with every NaN above +inf (a NaN candidate is its row's maximum, as in
 // torch.max), low half = ~index.  Every word of a real candidate is > 0, so 0 = "no candidate", and partial maxima combine

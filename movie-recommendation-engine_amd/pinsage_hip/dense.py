@@ -783,6 +783,35 @@ def row_dot(A, ia, B, ib):
     return out
 
 
+def rerank_max_candidates():
+    """the longest candidate list rerank_topk takes (ps_rerank_max_candidates: the library's own figure)"""
+    return int(nv.lib().ps_rerank_max_candidates())
+
+
+def rerank_topk(E, Q, cand, k, id_offset=0):
+    """The second level of a two-level search (ps_rerank_topk): cand int64 [nq, R] holds every query's candidate ids as a
+    first-level search returned them (hamming_topk; -1 pads and ids outside id_offset .. id_offset + N - 1 are skipped, an id
+    listed twice counts once) -> (vals fp32 [nq, k], ids int64 [nq, k]): the k best candidates by the exact inner product
+    Q[i] . E[id - id_offset], in dot_topk's order (descending, ties by ascending id) and with its bits, padded with (-inf, -1)."""
+    E, Q = _fp32_rows(E), _fp32_rows(Q)
+    if E.size(1) != Q.size(1):
+        raise ValueError(f"shape mismatch: E {tuple(E.shape)} vs Q {tuple(Q.shape)}")
+    if cand.dim() != 2 or cand.size(0) != Q.size(0):
+        raise ValueError(f"cand must be [nq, R] with one row per query, got {tuple(cand.shape)} for {Q.size(0)} queries")
+    if k < 1:
+        raise ValueError(f"k must be positive, got {k}")
+    cand = cand.to(device=E.device, dtype=torch.int64).contiguous()
+    nq, R = cand.size(0), cand.size(1)
+    if not 1 <= R <= rerank_max_candidates():
+        raise ValueError(f"rerank_topk takes 1 .. {rerank_max_candidates()} candidates per query, got {R}")
+    vals = torch.empty((nq, k), dtype=torch.float32, device=E.device)
+    ids = torch.empty((nq, k), dtype=torch.int64, device=E.device)
+    with torch.cuda.device(E.device):
+        nv.call("ps_rerank_topk", nv.ptr(E), E.size(0), E.size(1), int(id_offset), nv.ptr(Q), nq, nv.ptr(cand), R, int(k),
+                nv.ptr(vals), nv.ptr(ids), nv.stream())
+    return vals, ids
+
+
 def rank_count(E, Q, thr, tid, id_offset=0, count=None):
     """count[i] += #{items j of E (ids id_offset + j) that precede (thr[i], tid[i]) in dot_topk's order of Q[i] . E^T}
     (ps_rank_count: similarity descending by float key, ties by ascending id).  One GEMM with a counting epilogue, no [nq, N]

@@ -108,6 +108,8 @@ PROTOTYPES = {
     "ps_dot_topk": "i pqipqiipppzp",
     "ps_row_dot": "i pqpqippqpp",
     "ps_rank_count": "i pqiqpqpppp",
+    "ps_rerank_max_candidates": "i",
+    "ps_rerank_topk": "i pqiqpqpiippp",
     "ps_l2_topk_workspace_bytes": "z qqii",
     "ps_l2_topk": "i pqipqippipppzp",
     "ps_ivf_topk_workspace_bytes": "z qqiiiiq",
