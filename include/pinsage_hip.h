@@ -162,6 +162,34 @@ int ps_walk_paths(const int64_t *rowptr, const int32_t *col, const double *cdf, 
                   const int64_t *uoff, uint64_t seed, uint32_t call, int walk_mod,
                   const uint32_t *nodeinfo, const int32_t *guide, int32_t *paths, ps_stream_t stream);
 
+/* Node2vec-biased walks: RandomWalkSampler's p (return) and q (in-out), csrc/walk_biased.hip.  ps_walk_paths with one change: on
+ * every step that has a previous node t (the second step of a walk onwards) the weights of the row v the walk stands on are
+ * multiplied elementwise by alpha before `probabilities = weights / weights.sum()` (utils/random_walk.py:76), alpha of the edge
+ * v -> x being  bias[0] = 1/p if x == t,  else 1.0 if t has an out-edge to x,  else bias[1] = 1/q  (parallel edges are judged by
+ * their destination).  The rest is numpy's, as in ps_cdf_build: w * alpha one fp64 rounding, numpy's pairwise sum, the
+ * sequential cumsum, cdf /= cdf[-1], pick = searchsorted(cdf, u, 'right'); one uniform per step taken, none at a sink.  The first
+ * step has no previous node and is searched in `cdf`.  bias = {1, 1} gives ps_walk_paths' paths bit for bit.
+ * wsorted double[E] (ps_csr_build), nbr_sorted int32[E]: every row's destinations in ascending order, duplicates kept (the set
+ * test is a binary search in t's row).  bias: a DEVICE array of two doubles -- it is not read on the host, so an entry that is
+ * not finite and positive is answered on the device: every path of the call is -1 throughout.  PS_RNG_STREAM: walk i, step s
+ * reads uniforms[uoff[i] + s] (uoff int64[B], one stream position per walk); PS_RNG_PHILOX and walk_mod as in ps_walk_paths.
+ * A start, a previous node or a row offset outside the graph is an isolated node: nothing is read for it.
+ * One wave per walk; a step costs O(deg(v) log deg(t)) and O(deg(v)) of it is a sequential fp64 chain (the cumsum).  No
+ * workspace.  paths int32[B,L] (-1 after a sink).  PS_OK for B == 0; PS_EINVAL for L < 1 or (B > 0) a null pointer.
+ *
+ * ps_paths_topk: the visit counting and top-T cut of ps_walk_sample over GIVEN paths: paths int32[B, n] (the n = W * L entries of
+ * a start node, walk 0's steps first; negative entries are skipped) -> ids int32[B,T] (-1 pad), counts int32[B,T] (0 pad),
+ * nvalid int32[B], ordered by count descending, ties by first visit.  One wave per start node, the entries in LDS.
+ * n above ps_paths_topk_max_entries() (4096): PS_EUNSUPPORTED; PS_OK for B == 0; PS_EINVAL for n < 1, T < 1 or (B > 0) a null
+ * pointer. */
+int ps_walk_paths_biased(const int64_t *rowptr, const int32_t *col, const double *wsorted, const double *cdf,
+                         const int32_t *nbr_sorted, int64_t V, const int64_t *starts, int64_t B, int L, int rng_mode,
+                         const double *uniforms, const int64_t *uoff, uint64_t seed, uint32_t call, int walk_mod,
+                         const double *bias, int32_t *paths, ps_stream_t stream);
+int ps_paths_topk_max_entries(void);
+int ps_paths_topk(const int32_t *paths, int64_t B, int n, int T, int32_t *ids, int32_t *counts, int32_t *nvalid,
+                  ps_stream_t stream);
+
 /* Offsets into the numpy stream: uoff[i] = W*L * #{j < i : outdeg(starts[j]) > 0};
  * total[0] = uniforms consumed by the whole batch. */
 int ps_uniform_offsets(const int64_t *rowptr, int64_t V, const int64_t *starts, int64_t B, int W, int L,

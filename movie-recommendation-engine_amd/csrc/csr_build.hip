@@ -47,6 +47,9 @@ __global__ void gather_kernel(const uint32_t *perm, const int64_t *dst, const fl
 }
 
 // ---- numpy ndarray.sum() for a contiguous fp64 vector (see oracle/pinsage_oracle.py) --------
+// (csrc/walk_biased.hip holds the wave-shared twin of this tree -- leaf_sum / block_sum, the eight running sums of a leaf over
+// eight lanes -- for rows whose weights exist only per walk step; a change here is a change there.  tests/test_hip_biased_walk.py
+// holds the two to each other: with bias {1, 1} a biased step must pick what this file's CDF picks, on rows of 1 .. 8300 edges.)
 __device__ double pairwise_leaf(const double *a, int64_t n) {   // n <= 128
     if (n < 8) {
         double res = 0.0;

@@ -100,6 +100,21 @@ class DeviceGraph:
         self.has_reachable_sink = bool(f[0])
         self.max_degree = int(f[1])
         self.wsorted = wsorted
+        self.nbr_sorted = None
+
+    def sorted_neighbors(self):
+        """int32[E]: every row's destinations in ascending order, duplicates kept -- what the biased walk (ps_walk_paths_biased)
+        searches for "the previous node has an out-edge to x".  One torch sort of (row, col) keys, on the first biased call;
+        a sampler with p == q == 1 never builds it."""
+        if self.col is None or self.wsorted is None or self.cdf is None:
+            gone = [k for k in ("col", "cdf", "wsorted") if getattr(self, k) is None]
+            raise ValueError(f"the biased walk (p or q != 1) needs the plain col / cdf / wsorted arrays; {', '.join(gone)} "
+                             "dropped by compact() (expand() restores col and cdf from the packed blocks, not wsorted)")
+        if self.nbr_sorted is None:
+            rows = torch.repeat_interleave(torch.arange(self.V, device=self.device), self.rowptr[1:] - self.rowptr[:-1])
+            key = torch.sort(rows * max(self.V, 1) + self.col.to(torch.int64)).values
+            self.nbr_sorted = (key - rows * max(self.V, 1)).to(torch.int32).contiguous()
+        return self.nbr_sorted
 
     def compact(self):
         """Drop the plain `col` / `cdf` / `guide` arrays (16 bytes per edge): the walk kernels read the same values from the
@@ -110,6 +125,7 @@ class DeviceGraph:
             return self
         self.col = self.cdf = self.guide = None
         self.wsorted = None
+        self.nbr_sorted = None               # (the biased walk's table: it cannot run without col / wsorted)
         return self
 
     def expand(self):

@@ -56,6 +56,9 @@ PROTOTYPES = {
     "ps_walk_sample": "i pppqpqiiiippQIppppppppp",
     "ps_walk_sample_layers": "i pppqpqiiiippqQIpppppipppp",
     "ps_walk_paths": "i pppqpqiippQIipppp",
+    "ps_walk_paths_biased": "i pppppqpqiippQIippp",
+    "ps_paths_topk_max_entries": "i",
+    "ps_paths_topk": "i pqiipppp",
     "ps_uniform_offsets": "i pqpqiippp",
     "ps_mt19937_chunk_log2": "i",
     "ps_mt19937_window_shift": "i",

@@ -5,7 +5,8 @@ the nodes visited by 100 `_single_walk` calls by visit count (dict order = first
 picks negatives from a rank window with `np.random.choice`, everything on the process-global numpy RNG.
 Here the 100 walks + ranking of one query are one ps_walk_sample launch (T = 100 * walk_length keeps the whole
 ranking); the host-side `np.random.choice` calls are made exactly as in the reference and in the same order, so
-with rng='numpy' the returned indices and the final RNG state are identical to the reference's."""
+with rng='numpy' the returned indices and the final RNG state are identical to the reference's.  A sampler with p or q other
+than 1 ranks by its biased walks (the reference ranks with the sampler's own `_single_walk`)."""
 from __future__ import annotations
 
 import numpy as np
@@ -27,7 +28,7 @@ def sample_hard_negatives(sampler, num_movies, query_indices, num_hard_samples=5
         call = sampler._calls
         sampler._calls += 1
         batch = sampling.walk_sample(sampler.graph, [int(idx)], NUM_WALKS * L, W=NUM_WALKS, L=L, rng=sampler.rng,
-                                     seed=sampler.seed, call=call)
+                                     seed=sampler.seed, call=call, p=getattr(sampler, "p", 1.0), q=getattr(sampler, "q", 1.0))
         ids, _, nvalid, _ = batch.host()
         ranked = ids[0, : int(nvalid[0])]                                   # by count desc, first visit first
         candidates = [int(v) for v in ranked[min_rank:max_rank] if v < num_movies]   # `item in all_movie_indices`

@@ -6,6 +6,7 @@ counterpart with fp64 weights (personalized PageRank);
 (utils/random_walk.py:119-142), materialised only when python code actually looks at it."""
 from __future__ import annotations
 
+import math
 import os
 
 import numpy as np
@@ -219,21 +220,82 @@ def _sink_stream(graph, starts, W, L, uniforms=None):
     return uniforms, off
 
 
+def is_biased(p, q):
+    """does (p, q) ask for the second-order (node2vec) walk?  p == q == 1 is the reference's first-order walk and runs the kernels it always ran"""
+    return not (p == 1.0 and q == 1.0)
+
+
+def check_bias(p, q):
+    """(1 / p, 1 / q) as python floats; p (return) and q (in-out) must be finite and greater than 0, and so must their inverses"""
+    try:
+        p, q = float(p), float(q)
+        ok = math.isfinite(p) and math.isfinite(q) and p > 0 and q > 0 and math.isfinite(1.0 / p) and math.isfinite(1.0 / q)
+    except (TypeError, ValueError, ZeroDivisionError):
+        ok = False
+    if not ok:
+        raise ValueError(f"p and q must be finite and greater than 0, got p={p!r}, q={q!r}")
+    return 1.0 / p, 1.0 / q
+
+
+def _no_biased_sinks(graph, rng):
+    if rng == "numpy" and graph.has_reachable_sink:
+        raise NotImplementedError("biased walks (p or q != 1) with rng='numpy' on a graph with reachable sinks are not implemented: "
+                                  "a walk that stops early shifts every later stream position.  Use rng='philox' there.")
+
+
+def _biased_paths(graph, walks, L, mode, uniforms, uoff, seed, call, walk_mod, p, q):
+    """ps_walk_paths_biased over `walks` (int64 start node per walk) -> int32[len(walks), L]"""
+    dev = graph.device
+    inv_p, inv_q = check_bias(p, q)
+    nbr = graph.sorted_neighbors()
+    bias = torch.tensor([inv_p, inv_q], dtype=torch.float64, device=dev)
+    n = int(walks.numel())
+    paths = torch.empty((n, L), dtype=torch.int32, device=dev)
+    nv.call("ps_walk_paths_biased", nv.ptr(graph.rowptr), nv.ptr(graph.col), nv.ptr(graph.wsorted), nv.ptr(graph.cdf), nv.ptr(nbr),
+            graph.V, nv.ptr(walks), n, L, mode, nv.ptr(uniforms), nv.ptr(uoff), seed & (2 ** 64 - 1), call, walk_mod, nv.ptr(bias),
+            nv.ptr(paths), nv.stream())
+    return paths
+
+
+def paths_topk_max_entries():
+    """the most entries (W * L) per start node that ps_paths_topk counts"""
+    return int(nv.lib().ps_paths_topk_max_entries())
+
+
+def paths_topk(paths, T):
+    """NeighborBatch of given paths int32[B, n] (n = W * L, walk-major, -1 entries skipped): ps_walk_sample's counting and cut"""
+    B, n = int(paths.size(0)), int(paths.size(1))
+    dev = paths.device
+    ids = torch.empty((B, T), dtype=torch.int32, device=dev)
+    counts = torch.empty((B, T), dtype=torch.int32, device=dev)
+    nvalid = torch.empty(B, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        nv.call("ps_paths_topk", nv.ptr(paths), B, n, T, nv.ptr(ids), nv.ptr(counts), nv.ptr(nvalid), nv.stream())
+    return NeighborBatch(ids, counts, nvalid)
+
+
 def walk_sample(graph, nodes, T, W=100, L=2, rng="numpy", seed=0, call=0, uniforms=None, use_guide=True, use_packed=True, use_buckets=True,
-                stream_nodes=None, use_dest=True):
+                stream_nodes=None, use_dest=True, p=1.0, q=1.0):
     """batch_sample_neighbors on the device.  rng='numpy': the global numpy stream (bit-exact with
     the reference; graphs with reachable sinks take the per-walk stream positions of sink_walk_offsets);
     rng='philox': counter-based.
     `uniforms` (device fp64) overrides the numpy draw (tests).  `stream_nodes` (rng='numpy' only): the complete
     start-node sequence of the logical batch this call is a contiguous slice of (item shards): the stream offsets
     are computed over all of them and the whole batch's uniforms are drawn, so the ids/counts equal the matching
-    rows of the unsharded call and the global np.random state ends where the unsharded call leaves it."""
+    rows of the unsharded call and the global np.random state ends where the unsharded call leaves it.
+    p / q other than 1 (node2vec's return and in-out parameters): the W walks of every start node are walked by
+    ps_walk_paths_biased, at the stream positions / Philox counters the first-order kernel gives them, and counted by
+    ps_paths_topk; the accelerator switches (use_*) do not apply.  p == q == 1 changes nothing."""
     dev = graph.device
+    biased = is_biased(p, q)
+    if biased:
+        check_bias(p, q)
+        _no_biased_sinks(graph, rng)
+        if W * L > paths_topk_max_entries():
+            raise ValueError(f"a biased sampler (p or q != 1) counts at most {paths_topk_max_entries()} visits per start node "
+                             f"(ps_paths_topk); num_walks * walk_length = {W} * {L} = {W * L}")
     starts = _nodes_tensor(nodes, dev, graph.V)
     B = int(starts.numel())
-    ids = torch.empty((B, T), dtype=torch.int32, device=dev)
-    counts = torch.empty((B, T), dtype=torch.int32, device=dev)
-    nvalid = torch.empty(B, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         if rng == "numpy" and graph.has_reachable_sink:
             # data-dependent RNG consumption (utils/random_walk.py:65-69): per-walk stream positions by fixpoint
@@ -266,6 +328,15 @@ def walk_sample(graph, nodes, T, W=100, L=2, rng="numpy", seed=0, call=0, unifor
             uoff, uniforms, mode = None, None, nv.PS_RNG_PHILOX
         else:
             raise ValueError("rng must be 'numpy' or 'philox'")
+        if biased:
+            woff = None
+            if uoff is not None:                                 # walk w of start i: uoff[i] + w * L
+                woff = (uoff[:, None] + torch.arange(W, dtype=torch.int64, device=dev)[None, :] * L).reshape(-1).contiguous()
+            paths = _biased_paths(graph, starts.repeat_interleave(W).contiguous(), L, mode, uniforms, woff, seed, call, W, p, q)
+            return paths_topk(paths.view(B, W * L), T)
+        ids = torch.empty((B, T), dtype=torch.int32, device=dev)
+        counts = torch.empty((B, T), dtype=torch.int32, device=dev)
+        nvalid = torch.empty(B, dtype=torch.int32, device=dev)
         packed = use_guide and use_packed
         nv.call("ps_walk_sample", nv.ptr(graph.rowptr), nv.ptr(graph.col), nv.ptr(graph.cdf), graph.V, nv.ptr(starts), B, W, L, T,
                 mode | (graph.walk_flags if (use_guide and use_buckets) else 0), nv.ptr(uniforms), nv.ptr(uoff),
@@ -293,15 +364,17 @@ def _range_nodes(start, stop, dev):
 
 
 def walk_sample_layers(graph, nodes, T, layers, W=100, L=2, rng="numpy", seed=0, call=0, uniforms=None,
-                       stream_nodes=None, defer_state=False):
+                       stream_nodes=None, defer_state=False, p=1.0, q=1.0):
     """`layers` consecutive batch_sample_neighbors calls over the same start nodes (PinSage.get_embeddings,
     model/pinsage.py:271-275) as ONE kernel launch (ps_walk_sample_layers) -> list of NeighborBatch.  Bit-identical
     to `layers` walk_sample calls: Philox uses call, call + 1, ...; rng='numpy' draws all layers' uniforms from the
     global stream in one go (layer 0's, then layer 1's, ... as the reference consumes them) and hands the state back
     once.  `nodes` may be a python range (no host sync in the steady state).  defer_state=True leaves that hand-back to
-    dense.finish_rng_state(), which the caller must invoke before it returns to user code."""
+    dense.finish_rng_state(), which the caller must invoke before it returns to user code.
+    p / q other than 1: `layers` consecutive biased walk_sample calls, each drawing from where the previous one left
+    np.random (the order of the reference's consecutive calls); the state is handed back before returning, whatever defer_state."""
     dev = graph.device
-    if rng == "numpy" and graph.has_reachable_sink:
+    if is_biased(p, q) or (rng == "numpy" and graph.has_reachable_sink):
         # a walk that reaches a sink consumes fewer uniforms: the layers are drawn one after the other, each from where the
         # previous one left the stream (what consecutive batch_sample_neighbors calls do in the reference)
         nd = torch.arange(nodes.start, nodes.stop, dtype=torch.int64, device=dev) if isinstance(nodes, range) else nodes
@@ -309,7 +382,7 @@ def walk_sample_layers(graph, nodes, T, layers, W=100, L=2, rng="numpy", seed=0,
         if stream_nodes is not None:
             a0 = stream_nodes[0]
             sn = (torch.arange(a0.start, a0.stop, dtype=torch.int64, device=dev) if isinstance(a0, range) else a0, stream_nodes[1])
-        return [walk_sample(graph, nd, T, W, L, rng=rng, seed=seed, call=call + r, uniforms=None, stream_nodes=sn)
+        return [walk_sample(graph, nd, T, W, L, rng=rng, seed=seed, call=call + r, uniforms=None, stream_nodes=sn, p=p, q=q)
                 for r in range(layers)]
     as_range = nodes if isinstance(nodes, range) else None
     if as_range is not None:
@@ -382,9 +455,13 @@ def walk_sample_layers(graph, nodes, T, layers, W=100, L=2, rng="numpy", seed=0,
     return [NeighborBatch(ids[r], counts[r], nvalid[r]) for r in range(layers)]
 
 
-def walk_paths(graph, starts, L, rng="numpy", seed=0, call=0, walk_mod=0):
-    """One walk per start node: int32[B,L] visited nodes (-1 after a sink)."""
+def walk_paths(graph, starts, L, rng="numpy", seed=0, call=0, walk_mod=0, p=1.0, q=1.0):
+    """One walk per start node: int32[B,L] visited nodes (-1 after a sink).  p / q other than 1: ps_walk_paths_biased."""
     dev = graph.device
+    biased = is_biased(p, q)
+    if biased:
+        check_bias(p, q)
+        _no_biased_sinks(graph, rng)
     st = _nodes_tensor(starts, dev, graph.V)
     B = int(st.numel())
     paths = torch.empty((B, L), dtype=torch.int32, device=dev)
@@ -400,6 +477,8 @@ def walk_paths(graph, starts, L, rng="numpy", seed=0, call=0, walk_mod=0):
             mode = nv.PS_RNG_STREAM
         else:
             uoff, uniforms, mode = None, None, nv.PS_RNG_PHILOX
+        if biased:
+            return _biased_paths(graph, st, L, mode, uniforms, uoff, seed, call, walk_mod, p, q)
         nv.call("ps_walk_paths", nv.ptr(graph.rowptr), nv.ptr(graph.col), nv.ptr(graph.cdf), graph.V, nv.ptr(st), B, L, mode,
                 nv.ptr(uniforms), nv.ptr(uoff), seed & (2 ** 64 - 1), call, walk_mod, nv.ptr(graph.nodeinfo), nv.ptr(graph.guide),
                 nv.ptr(paths), nv.stream())

@@ -133,12 +133,21 @@ def fused_self_update(ops, P, i, H):
     return W1, b1
 
 
+def refuse_biased(sampler):
+    """The sharded pipeline samples first-order walks only (its fused launch, ps_walk_sample_layers, has no biased form): a
+    sampler that asks for p or q other than 1 is refused, never sampled unbiased in silence."""
+    if sampling.is_biased(getattr(sampler, "p", 1.0), getattr(sampler, "q", 1.0)):
+        raise ValueError(f"the sharded pipeline does not sample biased walks (p={sampler.p!r}, q={sampler.q!r}): "
+                         "use a sampler with p == q == 1, or the unsharded model")
+
+
 class HipOps:
     """The production backend: thin names over the C-ABI wrappers."""
 
     def sample(self, sampler, nodes, T, shard=None):
         """shard = (num_items, lo): with the numpy-stream RNG every rank draws the whole catalogue's uniforms
         (same np.random seed on all ranks) and indexes them with the global offsets of its own nodes."""
+        refuse_biased(sampler)
         if shard is not None and getattr(sampler, "rng", None) == "numpy":
             M, lo = shard
             all_nodes = torch.arange(M, dtype=torch.int64, device=nodes.device)
@@ -147,6 +156,7 @@ class HipOps:
 
     def sample_layers(self, sampler, lo, hi, T, layers, shard=None):
         """all layers' samples of the item range [lo, hi) in one launch (ps_walk_sample_layers)"""
+        refuse_biased(sampler)
         stream = None
         if shard is not None and getattr(sampler, "rng", None) == "numpy":
             stream = (range(shard[0]), shard[1])
@@ -203,6 +213,7 @@ class ShardedPinSage:
 
     def __init__(self, params, num_layers, sampler, num_items, ops=None, group=None, standin=None):
         """standin=(rank, world): play one rank of a `world`-rank job on this GPU without a process group (see Comm)."""
+        refuse_biased(sampler)
         self.P = params                   # state_dict tensors (replicated), on the compute device
         self.num_layers = num_layers
         self.sampler = sampler

@@ -6,6 +6,7 @@ per-node loops are replaced by one kernel launch per batch:
   _prepare_adjacency_list (:33-50)      -> ps_csr_build + ps_cdf_build (CSR + fp64 CDF in HBM)
   _single_walk (:52-83)                 -> ps_walk_paths
   sample_neighbors / batch_sample_neighbors (:85-142) -> ps_walk_sample
+  p / q other than 1 (stored and never read by the reference) -> ps_walk_paths_biased + ps_paths_topk: the node2vec walk
   compute_ppr_matrix / precompute_top_neighbors (:144-229) -> ps_ppr_shares + ps_ppr_push + ps_ppr_topk
 With rng='numpy' (default) the sampler consumes the process-global `np.random` stream exactly
 like the reference (same ids, same fp64 weights, same RNG state afterwards).
@@ -28,6 +29,7 @@ class RandomWalkSampler:
         self.num_walks = num_walks
         self.p = p
         self.q = q
+        self._check_bias()
         self.rng = rng
         self.seed = int(seed)
         self._calls = 0
@@ -37,12 +39,19 @@ class RandomWalkSampler:
     def _prepare_adjacency_list(self, device=None):
         self.graph = DeviceGraph(self.edge_index, self.edge_weights, device=device)
 
+    def _check_bias(self):
+        """p (return) and q (in-out) steer every step after a walk's first (include/pinsage_hip.h: ps_walk_paths_biased); both 1
+        is the reference's first-order walk and is not looked at further"""
+        if sampling.is_biased(self.p, self.q):
+            sampling.check_bias(self.p, self.q)
+
     @classmethod
-    def from_graph(cls, graph, walk_length=2, num_walks=100, rng="numpy", seed=0):
+    def from_graph(cls, graph, walk_length=2, num_walks=100, rng="numpy", seed=0, p=1.0, q=1.0):
         """A sampler over an already built DeviceGraph (shares the CSR/CDF in HBM)."""
         self = cls.__new__(cls)
         self.edge_index = self.edge_weights = None
-        self.walk_length, self.num_walks, self.p, self.q = walk_length, num_walks, 1.0, 1.0
+        self.walk_length, self.num_walks, self.p, self.q = walk_length, num_walks, p, q
+        self._check_bias()
         self.rng, self.seed, self._calls, self._adj_list = rng, int(seed), 0, None
         self.graph = graph
         return self
@@ -67,7 +76,7 @@ class RandomWalkSampler:
         self._calls += 1
         return sampling.walk_sample(self.graph, nodes, int(num_neighbors), W=self.num_walks, L=self.walk_length,
                                     rng=self.rng, seed=self.seed, call=call, uniforms=uniforms,
-                                    stream_nodes=stream_nodes if self.rng == "numpy" else None)
+                                    stream_nodes=stream_nodes if self.rng == "numpy" else None, p=self.p, q=self.q)
 
     def sample_batches(self, nodes, num_neighbors=10, layers=2, stream_nodes=None, defer_state=False):
         """`layers` consecutive sample_batch calls over the same nodes in ONE launch (what PinSage.get_embeddings
@@ -78,13 +87,14 @@ class RandomWalkSampler:
         return sampling.walk_sample_layers(self.graph, nodes, int(num_neighbors), int(layers), W=self.num_walks,
                                            L=self.walk_length, rng=self.rng, seed=self.seed, call=call,
                                            stream_nodes=stream_nodes if self.rng == "numpy" else None,
-                                           defer_state=defer_state)
+                                           defer_state=defer_state, p=self.p, q=self.q)
 
     def single_walks(self, start_nodes):
         """Batched _single_walk: int32[B, walk_length] device tensor (-1 after a sink)."""
         call = self._calls
         self._calls += 1
-        return sampling.walk_paths(self.graph, start_nodes, self.walk_length, rng=self.rng, seed=self.seed, call=call)
+        return sampling.walk_paths(self.graph, start_nodes, self.walk_length, rng=self.rng, seed=self.seed, call=call,
+                                   p=self.p, q=self.q)
 
     # ---- reference API -------------------------------------------------------------------
     def _single_walk(self, start_node):
