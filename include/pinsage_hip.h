@@ -655,6 +655,32 @@ int ps_rerank_max_candidates(void);
 int ps_rerank_topk(const float *E, int64_t N, int D, int64_t id_offset, const float *Q, int64_t nq, const int64_t *cand, int R,
                    int k, float *vals, int64_t *ids, ps_stream_t stream);
 
+/* ---- minibatch blocks: the node set of one layer of a batch's K-hop neighbourhood (PinSage paper, Algorithm 2; the reference
+ * embeds the whole catalogue, model/pinsage.py:253-280), csrc/frontier.hip.
+ * ps_frontier_build: seeds int32[S] + a neighbour table ids int32[B,T] / nvalid int32[B] (ps_walk_sample's or ps_ppr_topk's)
+ * -> the nodes the layer reads, the seeds first, and the table renumbered into them.  B need not equal S.
+ *   Slot (i, j) is KEPT iff j < min(nvalid[i], T) and 0 <= ids[i,j] < limit: ps_importance_pool's keep rule with
+ *   max_idx = limit - 1 (a negative nvalid[i] means 0, one above T means T; a slot at or beyond nvalid[i] is never kept,
+ *   whatever id it holds, and no other id is used as an index).
+ *   frontier int32[S + min(B * T, limit)]: the S seeds in the given order, then every kept id that is not a seed, each once,
+ *   ascending.  count int32[1] = the number of entries written; the entries beyond it are left untouched.
+ *   local int32[B,T]: a kept slot gets the position of its id in `frontier` (a seed's id the seed's position), every other
+ *   slot -1.  S == 0: the sorted distinct kept ids, `local` the inverse map.  B == 0: the seeds alone (`local` is not touched).
+ *   The seeds are distinct and lie in [0, limit).  A seed outside that range is copied to `frontier` and never used as an
+ *   index; with such a seed, or one listed twice, frontier / count / local are unspecified, and every access still stays
+ *   inside the buffers as sized above.
+ *   Integer atomics (OR into a bitmap) and plain stores only, no float: the same inputs give the same bytes on every run,
+ *   however the atomics are scheduled.
+ *   PS_OK for S == 0 && B == 0 (count[0] = 0 if count is given), whatever the other pointers.  PS_EINVAL for T < 1, limit < 1,
+ *   a negative S or B, limit, B * T or S + min(B * T, limit) at or above 2^31 (positions are int32), or a null pointer on a
+ *   non-empty problem (seeds when S > 0; ids, nvalid, local when B > 0; frontier, count, workspace).  PS_EWORKSPACE for fewer
+ *   than ps_frontier_workspace_bytes(limit, S, B, T) bytes (0 for a shape that is PS_EINVAL): two bitmaps of `limit` bits, one
+ *   int32 per 32 768 ids and an int32 map of `limit` entries.  The workspace may hold anything on entry and is not preserved. */
+size_t ps_frontier_workspace_bytes(int64_t limit, int64_t S, int64_t B, int T);
+int ps_frontier_build(const int32_t *seeds, int64_t S, const int32_t *ids, const int32_t *nvalid, int64_t B, int T,
+                      int64_t limit, int32_t *frontier, int32_t *count, int32_t *local, void *workspace,
+                      size_t workspace_bytes, ps_stream_t stream);
+
 /* ---- next row: exact L2 / IVF search behind WeakANDIndex and benchmark_search_methods
  * (utils/nearest_neighbors.py:70-139, 176: faiss.IndexFlatL2 / faiss.IndexIVFFlat).
  * dist(q, x) = |q|^2 + |x|^2 - 2 q.x in fp32; k smallest by (distance, id), ascending; dist float[nq,k]

@@ -10,6 +10,9 @@ What runs where
   pooled branch (model/pinsage.py:217-240,248-249)   -> ps_importance_pool + ps_linear (fp32 MFMA,
         bias/ReLU/concat/L2-normalise fused); with autograd enabled the same kernel does the
         pooling forward and the dense layers are differentiable (last entry).
+  pooled branch over a batch only (not in the reference) -> PinSage.forward_blocks / embed_minibatch: the same layers over the
+        minibatch blocks of RandomWalkSampler.sample_blocks (ps_frontier_build), each layer only on the rows the next one needs;
+        with rng='philox' the rows of the full-catalogue forward bit for bit (DESIGN.md §4 "Minibatch blocks").
   MLP branch (:205-214, what train.py uses)           -> nn.Linear as in the reference; under autograd on the GPU, last entry.
   edge_index branch (:243-245, GraphConv)             -> ps_spmm_csr over the edges grouped by target node (no grad); under
         autograd ps_spmm_csr_exact forward, the same kernel over the source-grouped edges and ps_sddmm_csr backward
@@ -309,6 +312,60 @@ class PinSage(nn.Module):
             h = dense.linear(h, W1, b1, x2=h_neigh, W2=Wu[:, H:], relu=True, l2norm=True)
         e = dense.linear(h, P["output_proj.weight"], P["output_proj.bias"], l2norm=True)
         return e if x.is_cuda else e.to(x.device)
+
+    # ---- minibatch (PinSage paper, Algorithm 2): the pooled branch over the K-hop blocks of a batch ----
+    @staticmethod
+    def _pool_block(h, block):
+        """h_neigh[n_dst, H] of a block over the n_src rows of h: ImportancePooling.forward's call for a device batch"""
+        if h.size(0) != block.n_src:
+            raise ValueError(f"the block reads {block.n_src} rows, the layer input has {h.size(0)}")
+        wts = None if block.wts is None else block.wts.to(h.device, torch.float32)     # fp64 rounded as the list path rounds (:140)
+        return sampling.pool(h, ids=block.ids, counts=block.counts, wts=wts, nvalid=block.nvalid)
+
+    def forward_blocks(self, x_in, blocks):
+        """The importance-pooled forward over minibatch blocks (pinsage_hip.minibatch.Block, blocks[0] the widest; from
+        RandomWalkSampler.sample_blocks): x_in [blocks[0].n_src, in] holds the features of blocks[0].src_nodes; layer i pools
+        over all n_src rows of its input and updates the first n_dst -- h = update(lin_self(h[:n_dst]), pool(h, blocks[i])) --
+        so the result is [blocks[-1].n_dst, out], one row per distinct seed.  A block's destinations are a prefix of its
+        sources: the self rows are a slice, nothing is gathered.
+        The arithmetic per row is that of `forward` over the whole catalogue: without gradients _forward_pooled_hip's (the
+        composed self-update weights, the two-operand dense.linear), with gradients the tape path (dense.linear on the tape,
+        sampling.pool; sampling.grad_method = "torch" keeps the torch layers)."""
+        if len(blocks) != self.num_layers:
+            raise ValueError(f"{self.num_layers} layers need {self.num_layers} blocks, got {len(blocks)}")
+        if self._needs_grad(x_in):
+            hip = _hip_linear("pooled", self, x_in)
+            h = _lin(self.input_proj, x_in, relu=True) if hip else F.relu(self.input_proj(x_in))
+            for i, block in enumerate(blocks):
+                h_neigh = self._pool_block(h, block)
+                conv = self.convs[i]
+                if hip:
+                    h = _lin_update(conv.lin_update, _lin(conv.lin_self, h[:block.n_dst]), h_neigh)
+                else:
+                    h = F.relu(conv.lin_update(torch.cat([conv.lin_self(h[:block.n_dst]), h_neigh], dim=1)))
+                    h = F.normalize(h, p=2, dim=1)
+            return _lin(self.output_proj, h, l2norm=True) if hip else F.normalize(self.output_proj(h), p=2, dim=1)
+        dev = nv.require_gpu()
+        xg = (x_in if x_in.is_cuda else x_in.to(dev)).float().contiguous()
+        P = {k: (v if v.device == xg.device else v.to(xg.device)).detach().float() for k, v in self.state_dict().items()}
+        h = dense.linear(xg, P["input_proj.weight"], P["input_proj.bias"], relu=True)
+        for i, block in enumerate(blocks):
+            h_neigh = self._pool_block(h, block)
+            H = h.size(1)
+            W1, b1 = fused_self_update(_OPS, P, i, H)
+            h = dense.linear(h[:block.n_dst], W1, b1, x2=h_neigh, W2=P[f"convs.{i}.lin_update.weight"][:, H:], relu=True, l2norm=True)
+        e = dense.linear(h, P["output_proj.weight"], P["output_proj.bias"], l2norm=True)
+        return e if x_in.is_cuda else e.to(x_in.device)
+
+    def embed_minibatch(self, x, random_walk_sampler, seeds, num_neighbors=10, source="walk"):
+        """Embeddings of the items `seeds` alone, [len(seeds), out] in the order requested (repeats allowed): the blocks of the
+        seeds' K-hop sampled neighbourhood (random_walk_sampler.sample_blocks over the x.size(0) items), the features of their
+        input nodes, forward_blocks.  x is the whole feature table; only the rows of the input nodes are read."""
+        input_nodes, inverse, blocks = random_walk_sampler.sample_blocks(seeds, num_neighbors, self.num_layers,
+                                                                         n_items=int(x.size(0)), source=source)
+        x_in = x.index_select(0, input_nodes.to(x.device, torch.int64))
+        out = self.forward_blocks(x_in, blocks)
+        return out[inverse.to(out.device)]
 
     def get_embeddings(self, x, random_walk_sampler, num_neighbors=10):
         """reference model/pinsage.py:253-280: fresh neighbour samples per layer, then the pooled forward."""

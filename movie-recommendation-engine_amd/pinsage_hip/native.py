@@ -113,6 +113,8 @@ PROTOTYPES = {
     "ps_rank_count": "i pqiqpqpppp",
     "ps_rerank_max_candidates": "i",
     "ps_rerank_topk": "i pqiqpqpiippp",
+    "ps_frontier_workspace_bytes": "z qqqi",
+    "ps_frontier_build": "i pqppqiqppppzp",
     "ps_l2_topk_workspace_bytes": "z qqii",
     "ps_l2_topk": "i pqipqippipppzp",
     "ps_ivf_topk_workspace_bytes": "z qqiiiiq",

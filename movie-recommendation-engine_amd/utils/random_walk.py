@@ -8,6 +8,7 @@ per-node loops are replaced by one kernel launch per batch:
   sample_neighbors / batch_sample_neighbors (:85-142) -> ps_walk_sample
   p / q other than 1 (stored and never read by the reference) -> ps_walk_paths_biased + ps_paths_topk: the node2vec walk
   compute_ppr_matrix / precompute_top_neighbors (:144-229) -> ps_ppr_shares + ps_ppr_push + ps_ppr_topk
+  sample_blocks (not in the reference: the K-hop blocks of a batch, PinSage paper Algorithm 2) -> the kernels above + ps_frontier_build
 With rng='numpy' (default) the sampler consumes the process-global `np.random` stream exactly
 like the reference (same ids, same fp64 weights, same RNG state afterwards).
 """
@@ -88,6 +89,41 @@ class RandomWalkSampler:
                                            L=self.walk_length, rng=self.rng, seed=self.seed, call=call,
                                            stream_nodes=stream_nodes if self.rng == "numpy" else None,
                                            defer_state=defer_state, p=self.p, q=self.q)
+
+    def sample_blocks(self, seeds, num_neighbors=10, layers=2, n_items=None, source="walk"):
+        """The minibatch blocks of `seeds` (PinSage paper, Algorithm 2) -> (input_nodes, inverse, blocks): `layers`
+        pinsage_hip.minibatch.Blocks, blocks[0] the widest; input_nodes = blocks[0].src_nodes (int32, global ids: the rows of
+        the feature table the forward reads); inverse int64[len(seeds)]: the row of the output that holds each requested seed.
+        The seeds are item ids in [0, n_items) (n_items=None: every node of the graph) and may repeat; one outside that range
+        raises ValueError.  Only ids below n_items enter a block (ImportancePooling's filter over a feature table of n_items rows).
+        The layers are sampled top-down and take `layers` consecutive call numbers, as sample_batches does: layer `layers - 1`
+        for the distinct seeds with call base + layers - 1, then layer i - 1 for blocks[i].src_nodes with call base + i - 1.
+        rng='philox' keys a node's walks by (seed; node, walk, step, call), so every block row equals that node's row of
+        sample_batches(range(n_items), num_neighbors, layers)[i]; rng='numpy' draws each layer as one sample_batch(nodes) call
+        in that order.  source="ppr": every layer's lists are ppr_batch(nodes, num_neighbors, max_target=n_items) -- no RNG, the
+        blocks carry `wts`.  p, q, walk_length and num_walks apply as in sample_batch."""
+        from pinsage_hip import minibatch
+        if source not in ("walk", "ppr"):
+            raise ValueError(f"source must be 'walk' or 'ppr', not {source!r}")
+        layers, T = int(layers), int(num_neighbors)
+        if layers < 1:
+            raise ValueError("sample_blocks needs at least one layer")
+        n_items = self.graph.V if n_items is None else int(n_items)
+        nodes, inverse = minibatch.unique_seeds(seeds, n_items, self.graph.device)
+        if source == "ppr":
+            def sample_layer(i, nodes):
+                b = self.ppr_batch(nodes, T, max_target=n_items)
+                return b.ids, b.nvalid, None, b.wts
+        else:
+            base = self._calls
+            self._calls += layers
+
+            def sample_layer(i, nodes):
+                b = sampling.walk_sample(self.graph, nodes, T, W=self.num_walks, L=self.walk_length, rng=self.rng, seed=self.seed,
+                                         call=base + i, p=self.p, q=self.q)
+                return b.ids, b.nvalid, b.counts, None
+        blocks = minibatch.build_blocks(nodes, sample_layer, layers, n_items)
+        return blocks[0].src_nodes, inverse, blocks
 
     def single_walks(self, start_nodes):
         """Batched _single_walk: int32[B, walk_length] device tensor (-1 after a sink)."""
