@@ -34,6 +34,17 @@ bool ps_allow_lds(K kernel, size_t bytes) {
     return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) ==
            hipSuccess;
 }
+// ... for launchers whose slot remembers nothing else: allow `bytes` for every kernel of the list on the current device,
+// once per device; false: no device slot, or the runtime refused
+template <typename... K>
+bool ps_allow_lds_once(PsPerDevice &done, size_t bytes, K... kernels) {
+    int dv = 0;
+    if (!ps_device_index(&dv)) return false;
+    if (done.get(dv)) return true;
+    if (!(ps_allow_lds(kernels, bytes) && ...)) return false;
+    done.set(dv, 1);
+    return true;
+}
 
 static inline int64_t ps_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // workspaces are carved in 256-byte units from the first 256-byte boundary at or after the caller's pointer

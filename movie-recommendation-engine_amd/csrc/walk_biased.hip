@@ -1,4 +1,4 @@
-// walk_biased.hip -- node2vec-biased random walks and visit counting from paths on gfx950.
+// walk_biased.hip -- node2vec-biased random walks on gfx950.
 //
 // ps_walk_paths_biased is ps_walk_paths (csrc/walk_sample.hip) with the second-order bias of RandomWalkSampler's p / q: on every
 // step that has a previous node t, the weights of the row the walk stands on are multiplied by alpha before
@@ -15,18 +15,16 @@
 //      ballot (the CDF is non-decreasing), its chain is replayed with lane j keeping entry j, and a second ballot gives the edge.
 // This file is compiled without FMA contraction (csrc/Makefile), like csr_build.hip: every product, sum and quotient is
 // rounded once, as numpy rounds it.
-//
-// ps_paths_topk counts the visits of given paths and writes what ps_walk_sample writes: one wave per start node, entries, an
-// open-addressing table and the count-class bitmap in LDS, classes of equal count swept from the highest down, inside a class
-// first-visit order by ballot and prefix popcount.
+// The per-step uniform (csrc/walk_rng.h) and the first step's search of the row's own CDF (csrc/walk_search.h) are the copies
+// ps_walk_paths uses.  The visits of the paths are counted by ps_paths_topk (csrc/walk_topk.hip).
 #include "ps_common.h"
 #include "walk_rng.h"
+#include "walk_search.h"
 
 namespace {
 
 constexpr int WB_CAP = 1024;        // rows of up to this many edges keep their w * alpha in LDS between the passes
 constexpr int CEND_CAP = 128;       // chunk-end accumulators kept (rows of up to 8192 edges; beyond, the chain is replayed from the last one kept)
-constexpr int PT_MAX_ENTRIES = 4096;
 
 struct BiasedArgs {
     const int64_t *rowptr;
@@ -166,23 +164,11 @@ __global__ __launch_bounds__(64) void walk_paths_biased_kernel(BiasedArgs a) {
             if (alive) safe_row(a.rowptr, a.V, E, cur, lo, hi);
             if (hi == lo) alive = false;                      // sink: the walk stops, no uniform is consumed
             if (alive) {
-                double u, u_odd;
-                if (a.rng_mode == PS_RNG_STREAM) {
-                    u = a.uniforms[ubase + st];
-                } else {
-                    philox_uniform2(a.k0, a.k1, (uint32_t)s, (uint32_t)(a.walk_mod > 0 ? i % a.walk_mod : i), (uint32_t)(st >> 1),
-                                    a.call, u, u_odd);
-                    if (st & 1) u = u_odd;
-                }
+                const double u = walk_step_uniform(a.rng_mode, a.uniforms, ubase, a.k0, a.k1, a.call, a.walk_mod, s, i, st);
                 const int64_t n = hi - lo;
                 int64_t pick = n - 1;
-                if (st == 0) {                                // no previous node: the row's own CDF
-                    int64_t l = 0, h = n;
-                    while (l < h) {
-                        const int64_t mid = l + ((h - l) >> 1);
-                        if (a.cdf[lo + mid] <= u) l = mid + 1; else h = mid;
-                    }
-                    if (l < n) pick = l;
+                if (st == 0) {                                // no previous node: the row's own CDF (no guide in this ABI)
+                    pick = cdf_search<int64_t>(a.cdf, nullptr, lo, hi, u) - lo;
                 } else {
                     int64_t tlo, thi;
                     safe_row(a.rowptr, a.V, E, prev, tlo, thi);
@@ -241,80 +227,6 @@ __global__ __launch_bounds__(64) void walk_paths_biased_kernel(BiasedArgs a) {
     }
 }
 
-struct TopkArgs {
-    const int32_t *paths;
-    int64_t B;
-    int n, T;
-    int32_t *ids, *counts, *nvalid;
-    int hs_log2, nbw;
-};
-
-__global__ __launch_bounds__(64) void paths_topk_kernel(TopkArgs a) {
-    extern __shared__ int32_t smem[];
-    const int lane = threadIdx.x;
-    const int HS = 1 << a.hs_log2;
-    const int n = a.n;
-    int32_t *pos = smem;                   // the visited ids in path order
-    int32_t *cr = pos + n;                 // the visit count at the first visit of a node, 0 elsewhere
-    int32_t *hkey = cr + n;
-    int32_t *hcnt = hkey + HS;
-    int32_t *hfirst = hcnt + HS;
-    uint32_t *bitmap = reinterpret_cast<uint32_t *>(hfirst + HS);
-    const uint64_t lanemask_lt = (1ull << lane) - 1ull;
-    for (int64_t i = blockIdx.x; i < a.B; i += gridDim.x) {
-        const int32_t *src = a.paths + i * n;
-        for (int p = lane; p < n; p += 64) { pos[p] = src[p]; cr[p] = 0; }
-        for (int h = lane; h < HS; h += 64) { hkey[h] = -1; hcnt[h] = 0; hfirst[h] = 0x7fffffff; }
-        for (int b = lane; b < a.nbw; b += 64) bitmap[b] = 0u;
-        ps_wave_lds_sync();
-        for (int p = lane; p < n; p += 64) {
-            const int32_t v = pos[p];
-            if (v < 0) continue;
-            uint32_t h = ((uint32_t)v * 2654435761u) >> (32 - a.hs_log2);
-            while (true) {
-                const int old = atomicCAS(&hkey[h], -1, v);
-                if (old == -1 || old == v) break;
-                h = (h + 1) & (uint32_t)(HS - 1);
-            }
-            atomicAdd(&hcnt[h], 1);
-            atomicMin(&hfirst[h], p);
-        }
-        ps_wave_lds_sync();
-        for (int h = lane; h < HS; h += 64) {
-            if (hkey[h] >= 0) {
-                const int c = hcnt[h];
-                cr[hfirst[h]] = c;
-                atomicOr(&bitmap[c >> 5], 1u << (c & 31));
-            }
-        }
-        ps_wave_lds_sync();
-        int32_t *oid = a.ids + i * a.T, *ocn = a.counts + i * a.T;
-        int emitted = 0;
-        for (int wd = a.nbw - 1; wd >= 0 && emitted < a.T; --wd) {
-            uint32_t bits = __builtin_amdgcn_readfirstlane(bitmap[wd]);
-            while (bits != 0u && emitted < a.T) {
-                const int b = 31 - __builtin_clz(bits);
-                bits &= ~(1u << b);
-                const int c = wd * 32 + b;
-                for (int base = 0; base < n && emitted < a.T; base += 64) {
-                    const int p = base + lane;
-                    const bool flag = p < n && cr[p] == c;
-                    const uint64_t mask = __ballot(flag);
-                    if (flag) {
-                        const int r = emitted + __popcll(mask & lanemask_lt);
-                        if (r < a.T) { oid[r] = pos[p]; ocn[r] = c; }
-                    }
-                    emitted += __popcll(mask);
-                }
-            }
-        }
-        const int nv = emitted < a.T ? emitted : a.T;
-        for (int t = nv + lane; t < a.T; t += 64) { oid[t] = -1; ocn[t] = 0; }
-        if (lane == 0) a.nvalid[i] = nv;
-        ps_wave_lds_sync();
-    }
-}
-
 }  // namespace
 
 extern "C" int ps_walk_paths_biased(const int64_t *rowptr, const int32_t *col, const double *wsorted, const double *cdf,
@@ -330,34 +242,6 @@ extern "C" int ps_walk_paths_biased(const int64_t *rowptr, const int32_t *col, c
                        (uint32_t)seed, (uint32_t)(seed >> 32), call, walk_mod, bias, paths};
     const int64_t grid = B > 256 * 256 ? 256 * 256 : B;        // 256 CUs x 16 resident one-wave workgroups (LDS), 16 rounds deep
     hipLaunchKernelGGL(walk_paths_biased_kernel, dim3((unsigned)grid), dim3(64), 0, ps_stream(stream), a);
-    PS_CHECK_LAUNCH();
-    return PS_OK;
-}
-
-extern "C" int ps_paths_topk_max_entries(void) { return PT_MAX_ENTRIES; }
-
-extern "C" int ps_paths_topk(const int32_t *paths, int64_t B, int n, int T, int32_t *ids, int32_t *counts, int32_t *nvalid,
-                             ps_stream_t stream) {
-    if (B < 0 || n < 1 || T < 1) return PS_EINVAL;
-    if (B == 0) return PS_OK;
-    if (!paths || !ids || !counts || !nvalid) return PS_EINVAL;
-    if (n > PT_MAX_ENTRIES) return PS_EUNSUPPORTED;
-    int hs_log2 = 6;
-    while ((1 << hs_log2) * 4 < 5 * n) ++hs_log2;             // table >= 1.25 n slots
-    const int nbw = (n >> 5) + 1;                             // counts 0 .. n
-    const TopkArgs a{paths, B, n, T, ids, counts, nvalid, hs_log2, nbw};
-    const size_t lds = ((size_t)2 * n + 3 * ((size_t)1 << hs_log2) + nbw) * sizeof(int32_t);
-    if (lds > 64 * 1024) {                                    // dynamic LDS beyond 64 KiB has to be allowed per kernel and device, once
-        static PsPerDevice done;
-        int dv = 0;
-        if (!ps_device_index(&dv)) return PS_ELAUNCH;
-        if (!done.get(dv)) {
-            if (!ps_allow_lds(paths_topk_kernel, 160 * 1024)) return PS_ELAUNCH;
-            done.set(dv, 1);
-        }
-    }
-    const int64_t grid = B > 256 * 256 ? 256 * 256 : B;
-    hipLaunchKernelGGL(paths_topk_kernel, dim3((unsigned)grid), dim3(64), lds, ps_stream(stream), a);
     PS_CHECK_LAUNCH();
     return PS_OK;
 }

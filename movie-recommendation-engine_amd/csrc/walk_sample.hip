@@ -8,14 +8,15 @@
 //                     the packed blocks / plain arrays as fallbacks (all bit-identical); with destination records
 //                     (ps_dest_info_build) the row of a walk's second node comes out of LDS with the first pick;
 //                     visited ids are staged in LDS in Counter-insertion order (walk-major).
-//   2. count phase  : an LDS open-addressing table keyed by node id gives every position its
-//                     visit count (ds atomics) and first-visit position (atomic min).
-//   3. select phase : classes of equal count are swept from the highest count down; inside a
-//                     class, a wave ballot + prefix popcount over positions gives the
-//                     first-visit rank, i.e. python's stable sorted(..., reverse=True)[:T] (:107).
+//   2. count phase, 3. select phase : visit_count / visit_select of csrc/walk_visits.h over the staged positions (the copy that
+//                     ps_paths_topk, csrc/walk_topk.hip, runs over given paths): the T most visited nodes, ties in first-visit order.
 // No global atomics, no inter-wave communication: results do not depend on scheduling.
+// The uniforms (ps_res53, Philox, the per-step fetch of ps_walk_paths) are csrc/walk_rng.h, the bucket index and the scalar
+// CDF search csrc/walk_search.h; csrc/walk_biased.hip uses the same.
 #include "ps_common.h"
 #include "walk_rng.h"
+#include "walk_search.h"
+#include "walk_visits.h"
 
 namespace {
 
@@ -49,19 +50,11 @@ struct WalkArgs {
     int split;                      // 1: a wave walks ONE round of a start node (wave index = round * B + node) instead of all of them
 };
 
-// PS_RNG_STREAM_RAW: the stream as the generator leaves it (untempered MT19937 state words); uniform i = words 2i, 2i+1,
-// tempered and combined like numpy's random_sample (genrand_res53) -- saves the separate conversion pass over the stream
-__device__ __forceinline__ uint32_t mt_temper(uint32_t y) {
-    y ^= (y >> 11);
-    y ^= (y << 7) & 0x9d2c5680u;
-    y ^= (y << 15) & 0xefc60000u;
-    y ^= (y >> 18);
-    return y;
-}
+// uniform i of the stream: a double, or (raw, PS_RNG_STREAM_RAW) the two untempered MT19937 words it is made of
 __device__ __forceinline__ double stream_uniform(const double *uniforms, int64_t i, bool raw) {
     if (!raw) return uniforms[i];
     const uint2 w = reinterpret_cast<const uint2 *>(uniforms)[i];
-    return ((double)(mt_temper(w.x) >> 5) * 67108864.0 + (double)(mt_temper(w.y) >> 6)) * (1.0 / 9007199254740992.0);
+    return ps_res53(mt_temper(w.x), mt_temper(w.y));
 }
 
 __device__ __forceinline__ int64_t uniform_i64(int64_t v) {
@@ -69,8 +62,6 @@ __device__ __forceinline__ int64_t uniform_i64(int64_t v) {
     uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
     return (int64_t)(((uint64_t)hi << 32) | lo);
 }
-
-constexpr int LIN_PROBES = 12;   // forward-scan probes after the guide lookup before falling back to bisection
 
 // (row start, out-degree) of node v: one 8-byte record when nodeinfo is present
 typedef uint32_t eidx_t;   // edge index: E < 2^32 is enforced by ps_csr_build
@@ -170,17 +161,11 @@ __device__ __forceinline__ void search_two(const Acc &acc, bool aliveA, eidx_t l
     int nA_ = LIN_PROBES, nB_ = LIN_PROBES;
     if (acc.has_guide()) {
         if (aliveA) {
-            const uint32_t deg = (uint32_t)(hiA - loA);
-            uint32_t j = (uint32_t)(uA * (double)deg);
-            if (j >= deg) j = deg - 1;
-            lA = loA + (eidx_t)acc.g(loA + j);
+            lA = loA + (eidx_t)acc.g(loA + cdf_bucket(loA, hiA, uA));
             nA_ = 0;
         }
         if (aliveB) {
-            const uint32_t deg = (uint32_t)(hiB - loB);
-            uint32_t j = (uint32_t)(uB * (double)deg);
-            if (j >= deg) j = deg - 1;
-            lB = loB + (eidx_t)acc.g(loB + j);
+            lB = loB + (eidx_t)acc.g(loB + cdf_bucket(loB, hiB, uB));
             nB_ = 0;
         }
     }
@@ -242,10 +227,7 @@ struct BucketHit {
     int32_t k0, k1, k2, k3;
 };
 __device__ __forceinline__ const unsigned char *bucket_of(const unsigned char *buckets, eidx_t lo, eidx_t hi, double u) {
-    const uint32_t deg = (uint32_t)(hi - lo);
-    uint32_t j = (uint32_t)(u * (double)deg);
-    if (j >= deg) j = deg - 1;
-    return buckets + (size_t)(lo + j) * 64;
+    return buckets + (size_t)(lo + cdf_bucket(lo, hi, u)) * 64;
 }
 __device__ __forceinline__ BucketHit bucket_load(const unsigned char *r) {
     const double2 q0 = reinterpret_cast<const double2 *>(r)[0];
@@ -305,18 +287,12 @@ __device__ __forceinline__ void search_two_half(const unsigned char *buckets, co
     float4 cA = make_float4(0.f, 0.f, 0.f, 0.f), cB = cA;
     int4 kA = make_int4(-1, -1, -1, -1), kB = kA;
     if (aliveA) {
-        const uint32_t deg = (uint32_t)(hiA - loA);
-        uint32_t j = (uint32_t)(uA * (double)deg);
-        if (j >= deg) j = deg - 1;
-        const unsigned char *r = buckets + (size_t)(loA + j) * 32;
+        const unsigned char *r = buckets + (size_t)(loA + cdf_bucket(loA, hiA, uA)) * 32;
         cA = reinterpret_cast<const float4 *>(r)[0];
         kA = reinterpret_cast<const int4 *>(r)[1];
     }
     if (aliveB) {
-        const uint32_t deg = (uint32_t)(hiB - loB);
-        uint32_t j = (uint32_t)(uB * (double)deg);
-        if (j >= deg) j = deg - 1;
-        const unsigned char *r = buckets + (size_t)(loB + j) * 32;
+        const unsigned char *r = buckets + (size_t)(loB + cdf_bucket(loB, hiB, uB)) * 32;
         cB = reinterpret_cast<const float4 *>(r)[0];
         kB = reinterpret_cast<const int4 *>(r)[1];
     }
@@ -328,22 +304,6 @@ __device__ __forceinline__ void search_two_half(const unsigned char *buckets, co
         search_two(acc, moreA, loA, hiA, uA, moreB, loB, hiB, uB, fA, fB);
         if (moreA) nA = fA;
         if (moreB) nB = fB;
-    }
-}
-
-// Start state of searchsorted(cdf[lo:hi], u, 'right'): with a guide table the search starts at the bucket
-// floor(u * deg) (guide = #{cdf <= (j-1)/deg} <= answer) and first scans forward; `n` counts probes.
-__device__ __forceinline__ void search_init(const int32_t *guide, const unsigned char *packed, eidx_t lo, eidx_t hi,
-                                            double u, eidx_t &l, int &n) {
-    l = lo;
-    n = LIN_PROBES;
-    if (guide || packed) {
-        const uint32_t deg = (uint32_t)(hi - lo);
-        uint32_t j = (uint32_t)(u * (double)deg);
-        if (j >= deg) j = deg - 1;
-        const eidx_t e = lo + j;
-        l = lo + (eidx_t)(packed ? reinterpret_cast<const int32_t *>(packed + (size_t)(e >> 3) * 128 + 96)[e & 7] : guide[e]);
-        n = 0;
     }
 }
 
@@ -376,13 +336,11 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void walk_sample_kernel(WalkA
     const int R = a.split ? 1 : a.rounds;                  // rounds walked by one wave
     const int per_wave = R * NP * 64 + a.region_words + a.bitmap_words;
     int32_t *posb_all = smem + wv * per_wave;               // visited ids of every round, [round][walk * L + step]
-    int32_t *hkey = posb_all + R * NP * 64;
+    int32_t *hkey = posb_all + R * NP * 64;                 // the staged row (walk phase), then the table (count phase)
     int32_t *hcnt = hkey + HS;
-    int32_t *hfirst = hcnt + HS;
-    uint32_t *bitmap = reinterpret_cast<uint32_t *>(hkey + a.region_words);
+    const VisitTable table{hkey, hcnt, hcnt + HS, reinterpret_cast<uint32_t *>(hkey + a.region_words), a.hs_log2,
+                           visit_bitmap_words(P)};
     const GlobalEdges grow{a.cdf, a.col, a.guide, a.packed};
-    const int nbw = (P >> 5) + 1;
-    const uint64_t lanemask_lt = (1ull << lane) - 1ull;
 
     const int64_t nwork = a.split ? a.B * a.rounds : a.B;
     for (int64_t wi = (int64_t)blockIdx.x * WAVES_PER_BLOCK + wv; wi < nwork; wi += (int64_t)gridDim.x * WAVES_PER_BLOCK) {
@@ -468,8 +426,8 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void walk_sample_kernel(WalkA
                 if (stream) {
                     if (pre) {
                         const uint32_t a0 = st ? pwA.z : pwA.x, a1 = st ? pwA.w : pwA.y, b0 = st ? pwB.z : pwB.x, b1 = st ? pwB.w : pwB.y;
-                        if (aliveA) uA = ((double)(mt_temper(a0) >> 5) * 67108864.0 + (double)(mt_temper(a1) >> 6)) * (1.0 / 9007199254740992.0);
-                        if (aliveB) uB = ((double)(mt_temper(b0) >> 5) * 67108864.0 + (double)(mt_temper(b1) >> 6)) * (1.0 / 9007199254740992.0);
+                        if (aliveA) uA = ps_res53(mt_temper(a0), mt_temper(a1));
+                        if (aliveB) uB = ps_res53(mt_temper(b0), mt_temper(b1));
                     } else if (perwalk) {
                         if (aliveA) uA = a.uniforms[a.uoff[i * a.W + wA] + st];
                         if (aliveB) uB = a.uniforms[a.uoff[i * a.W + wB] + st];
@@ -505,66 +463,11 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void walk_sample_kernel(WalkA
         const int32_t *posb = posb_all + rd * NP * 64;
         int32_t *oid = a.ids + ((int64_t)(rd0 + rd) * a.B + i) * a.T;
         int32_t *ocn = a.counts + ((int64_t)(rd0 + rd) * a.B + i) * a.T;
-        // ---------------- count phase -------------------------------------------------
-        for (int h = lane; h < HS; h += 64) { hkey[h] = -1; hcnt[h] = 0; hfirst[h] = 0x7fffffff; }
-        for (int b = lane; b < nbw; b += 64) bitmap[b] = 0u;
-        ps_wave_lds_sync();
-        // (inserting the NP positions of a lane together -- all pending compare-and-swaps of a probing round in flight, then the
-        // count / first-visit atomics in one batch -- measured 2-4 x SLOWER for this phase: 22 K / 37 K cycles against 9.9 K)
-        int32_t vid[NP], slot[NP];
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            const int p = j * 64 + lane;
-            vid[j] = posb[p];
-            slot[j] = -1;
-            if (vid[j] >= 0) {
-                uint32_t h = ((uint32_t)vid[j] * 2654435761u) >> (32 - a.hs_log2);
-                while (true) {
-                    const int old = atomicCAS(&hkey[h], -1, vid[j]);
-                    if (old == -1 || old == vid[j]) break;
-                    h = (h + 1) & (uint32_t)(HS - 1);
-                }
-                atomicAdd(&hcnt[h], 1);
-                atomicMin(&hfirst[h], p);
-                slot[j] = (int32_t)h;
-            }
-        }
-        ps_wave_lds_sync();
-        int32_t cr[NP];   // visit count if this position is the first visit of its node, else 0
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            cr[j] = 0;
-            if (slot[j] >= 0 && hfirst[slot[j]] == j * 64 + lane) {
-                cr[j] = hcnt[slot[j]];
-                atomicOr(&bitmap[cr[j] >> 5], 1u << (cr[j] & 31));
-            }
-        }
-        ps_wave_lds_sync();
+        // ---------------- count phase, select phase (csrc/walk_visits.h) ----------------
+        int32_t vid[NP], cr[NP];
+        visit_count<NP>(table, [posb](int p) { return posb[p]; }, vid, cr, lane);
         PS_WS_STAMP(7 + rd * 2);
-        // ---------------- select phase ------------------------------------------------
-        int emitted = 0;
-        for (int wd = nbw - 1; wd >= 0 && emitted < a.T; --wd) {
-            uint32_t bits = __builtin_amdgcn_readfirstlane(bitmap[wd]);
-            while (bits != 0u && emitted < a.T) {
-                const int b = 31 - __builtin_clz(bits);
-                bits &= ~(1u << b);
-                const int c = wd * 32 + b;
-#pragma unroll
-                for (int j = 0; j < NP; ++j) {
-                    const bool flag = cr[j] == c;
-                    const uint64_t mask = __ballot(flag);
-                    if (flag) {
-                        const int r = emitted + __popcll(mask & lanemask_lt);
-                        if (r < a.T) { oid[r] = vid[j]; ocn[r] = c; }
-                    }
-                    emitted += __popcll(mask);
-                }
-            }
-        }
-        const int nv = emitted < a.T ? emitted : a.T;
-        for (int t = nv + lane; t < a.T; t += 64) { oid[t] = -1; ocn[t] = 0; }
-        if (lane == 0) a.nvalid[(int64_t)(rd0 + rd) * a.B + i] = nv;
-        ps_wave_lds_sync();
+        visit_select<NP>(table, vid, cr, a.T, oid, ocn, a.nvalid, (int64_t)(rd0 + rd) * a.B + i, lane);
         PS_WS_STAMP(8 + rd * 2);
         }
     }
@@ -587,23 +490,8 @@ __global__ void walk_paths_kernel(const int64_t *rowptr, const int32_t *col, con
                 if (hi == lo) {
                     alive = false;
                 } else {
-                    double u, u_odd;
-                    if (rng_mode == PS_RNG_STREAM) {
-                        u = uniforms[ubase + st];
-                    } else {
-                        philox_uniform2(k0, k1, (uint32_t)s, (uint32_t)(walk_mod > 0 ? i % walk_mod : i), (uint32_t)(st >> 1), call, u, u_odd);
-                        if (st & 1) u = u_odd;
-                    }
-                    eidx_t l, h = hi;
-                    int n;
-                    search_init(guide, nullptr, lo, hi, u, l, n);
-                    while (l < h) {
-                        const eidx_t mid = (n < LIN_PROBES) ? l : l + ((h - l) >> 1);
-                        if (cdf[mid] <= u) l = mid + 1; else h = mid;
-                        ++n;
-                    }
-                    if (l >= hi) l = hi - 1;
-                    nxt = col[l];
+                    const double u = walk_step_uniform(rng_mode, uniforms, ubase, k0, k1, call, walk_mod, s, i, st);
+                    nxt = col[cdf_search<eidx_t>(cdf, guide, lo, hi, u)];
                     cur = nxt;
                 }
             }
@@ -717,10 +605,7 @@ static int walk_sample_launch(const int64_t *rowptr, const int32_t *col, const d
     if (dest_info && (!packed || reinterpret_cast<size_t>(dest_info) % 8 != 0)) return PS_EINVAL;
     const int64_t P = (int64_t)W * L;
     if (P > 4096) return PS_EUNSUPPORTED;                  // 64 positions per lane: registers (vid / slot / cr) and 160 KiB of LDS end here
-    int np = 1;
-    while (np * 64 < P) np <<= 1;
-    int hs_log2 = 6;
-    while ((1 << hs_log2) * 4 < 5 * P) ++hs_log2;      // table >= 1.25 P slots (load factor <= 0.8)
+    const int np = visit_np((int)P), hs_log2 = visit_table_log2((int)P);
     WalkArgs a{rowptr, col, cdf, V, starts, B, W, L, T, rng_mode, uniforms, uoff,
                (uint32_t)seed, (uint32_t)(seed >> 32), call, nodeinfo, guide, reinterpret_cast<const unsigned char *>(packed), ids, counts, nvalid, hs_log2, 0, 0, reinterpret_cast<const unsigned char *>(buckets), half_buckets, 0,
                rounds, round_stride, reinterpret_cast<const uint2 *>(dest_info), 0};
@@ -736,7 +621,7 @@ static int walk_sample_launch(const int64_t *rowptr, const int32_t *col, const d
     // LDS budget: the kernel holds 24 waves per CU by registers; 160 KB / 24 leaves ~6.6 KB per wave, and whatever
     // the position buffers and the hash table do not need of that lets longer start rows be staged.
     const int hash_words = 3 * (1 << hs_log2);
-    const int bitmap_words = P <= 1024 ? BITMAP_WORDS : (int)(((P >> 5) + 1 + 7) & ~7);
+    const int bitmap_words = P <= 1024 ? BITMAP_WORDS : (visit_bitmap_words((int)P) + 7) & ~7;
     a.bitmap_words = bitmap_words;
     // (8 KiB per wave -- what 20 resident waves leave -- stages 84 % of SYN-25M's start rows instead of 78 % and measured no faster,
     // r04: 364-397 us against 374-381 for the two-layer launch, alternating in one process; 9 KiB slower)
@@ -755,16 +640,9 @@ static int walk_sample_launch(const int64_t *rowptr, const int32_t *col, const d
     // dynamic LDS beyond 64 KiB (W * L > 1024 only) has to be allowed per kernel and device, once
 #define PS_WS_LAUNCH(NP_)                                                                                                      \
     do {                                                                                                                       \
-        if (lds > 64 * 1024) {                                                                                                 \
-            static PsPerDevice done;                                                                                           \
-            int dv = 0;                                                                                                        \
-            if (!ps_device_index(&dv)) return PS_ELAUNCH;                                                                      \
-            if (!done.get(dv)) {                                                                                               \
-                if (!ps_allow_lds(walk_sample_kernel<NP_, false>, 160 * 1024) ||                                               \
-                    !ps_allow_lds(walk_sample_kernel<NP_, true>, 160 * 1024)) return PS_ELAUNCH;                               \
-                done.set(dv, 1);                                                                                               \
-            }                                                                                                                  \
-        }                                                                                                                      \
+        static PsPerDevice done;                                                                                               \
+        if (lds > 64 * 1024 && !ps_allow_lds_once(done, 160 * 1024, walk_sample_kernel<NP_, false>, walk_sample_kernel<NP_, true>)) \
+            return PS_ELAUNCH;                                                                                                 \
         if (a.dest_info != nullptr && NP_ <= 4) {                                                                              \
             constexpr int ND = NP_ <= 4 ? NP_ : 4;      /* only these are instantiated with DEST */                                \
             if (rng_mode == PS_RNG_PHILOX)                                                                                     \
@@ -776,16 +654,7 @@ static int walk_sample_launch(const int64_t *rowptr, const int32_t *col, const d
         else                                                                                                                   \
             hipLaunchKernelGGL((walk_sample_kernel<NP_, true>), dim3((unsigned)grid), dim3(64 * WAVES_PER_BLOCK), lds, st, a);  \
     } while (0)
-    switch (np) {
-        case 1: PS_WS_LAUNCH(1); break;
-        case 2: PS_WS_LAUNCH(2); break;
-        case 4: PS_WS_LAUNCH(4); break;
-        case 8: PS_WS_LAUNCH(8); break;
-        case 16: PS_WS_LAUNCH(16); break;
-        case 32: PS_WS_LAUNCH(32); break;
-        case 64: PS_WS_LAUNCH(64); break;
-        default: return PS_EUNSUPPORTED;
-    }
+    PS_VISIT_NP_SWITCH(np, PS_WS_LAUNCH)
 #undef PS_WS_LAUNCH
     PS_CHECK_LAUNCH();
     return PS_OK;

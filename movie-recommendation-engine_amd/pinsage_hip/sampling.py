@@ -220,6 +220,44 @@ def _sink_stream(graph, starts, W, L, uniforms=None):
     return uniforms, off
 
 
+def _uniform_offsets(graph, starts, W, L):
+    """ps_uniform_offsets: (stream position of every start node on a sink-free graph int64[B], uniforms consumed int64[1])"""
+    dev = graph.device
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    uoff = torch.empty(starts.numel(), dtype=torch.int64, device=dev)
+    nv.call("ps_uniform_offsets", nv.ptr(graph.rowptr), graph.V, nv.ptr(starts), starts.numel(), W, L, nv.ptr(uoff), nv.ptr(total),
+            nv.stream())
+    return uoff, total
+
+
+def _stream_plan(graph, starts, W, L, rng, uniforms=None, stream_nodes=None):
+    """(uniforms, uoff, mode) of W walks of L steps from every node of `starts` (device int64): nothing for rng='philox'; for
+    rng='numpy' the global stream's uniforms (drawn here unless given) and one position per start node (PS_RNG_STREAM) or, on a
+    graph with reachable sinks, per walk (PS_RNG_STREAM_WALKS).  stream_nodes = (all nodes, lo): `starts` is the slice from `lo`
+    of that logical batch; positions and uniforms are those of all of it."""
+    if rng == "philox":
+        return None, None, nv.PS_RNG_PHILOX
+    if rng != "numpy":
+        raise ValueError("rng must be 'numpy' or 'philox'")
+    dev = graph.device
+    B = int(starts.numel())
+    all_t, lo = starts, 0
+    if stream_nodes is not None:
+        all_t, lo = _nodes_tensor(stream_nodes[0], dev, graph.V), stream_nodes[1]
+    if graph.has_reachable_sink:
+        # data-dependent RNG consumption (utils/random_walk.py:65-69): per-walk stream positions by fixpoint
+        uniforms, uoff = _sink_stream(graph, all_t, W, L, uniforms)
+        if stream_nodes is not None:
+            uoff = uoff[lo * W:(lo + B) * W].contiguous()
+        return uniforms, uoff, nv.PS_RNG_STREAM_WALKS
+    uoff, total = _uniform_offsets(graph, all_t, W, L)
+    if stream_nodes is not None:
+        uoff = uoff[lo:lo + B].contiguous()
+    if uniforms is None:
+        uniforms = draw_numpy_uniforms(int(total.item()), dev)
+    return uniforms, uoff, nv.PS_RNG_STREAM
+
+
 def is_biased(p, q):
     """does (p, q) ask for the second-order (node2vec) walk?  p == q == 1 is the reference's first-order walk and runs the kernels it always ran"""
     return not (p == 1.0 and q == 1.0)
@@ -297,37 +335,7 @@ def walk_sample(graph, nodes, T, W=100, L=2, rng="numpy", seed=0, call=0, unifor
     starts = _nodes_tensor(nodes, dev, graph.V)
     B = int(starts.numel())
     with torch.cuda.device(dev):
-        if rng == "numpy" and graph.has_reachable_sink:
-            # data-dependent RNG consumption (utils/random_walk.py:65-69): per-walk stream positions by fixpoint
-            if stream_nodes is not None:
-                all_nodes, lo = stream_nodes
-                all_t = _nodes_tensor(all_nodes, dev, graph.V)
-                uniforms, off_all = _sink_stream(graph, all_t, W, L, uniforms)
-                uoff = off_all[lo * W:(lo + B) * W].contiguous()
-            else:
-                uniforms, uoff = _sink_stream(graph, starts, W, L, uniforms)
-            mode = nv.PS_RNG_STREAM_WALKS
-        elif rng == "numpy":
-            total = torch.empty(1, dtype=torch.int64, device=dev)
-            if stream_nodes is not None:
-                all_nodes, lo = stream_nodes
-                all_nodes = _nodes_tensor(all_nodes, dev, graph.V)
-                uoff_all = torch.empty(all_nodes.numel(), dtype=torch.int64, device=dev)
-                nv.call("ps_uniform_offsets", nv.ptr(graph.rowptr), graph.V, nv.ptr(all_nodes), all_nodes.numel(), W, L,
-                        nv.ptr(uoff_all), nv.ptr(total), nv.stream())
-                uoff = uoff_all[lo:lo + B].contiguous()
-            else:
-                uoff = torch.empty(B, dtype=torch.int64, device=dev)
-                nv.call("ps_uniform_offsets", nv.ptr(graph.rowptr), graph.V, nv.ptr(starts), B, W, L, nv.ptr(uoff), nv.ptr(total),
-                        nv.stream())
-            if uniforms is None:
-                n = int(total.item())
-                uniforms = draw_numpy_uniforms(n, dev)
-            mode = nv.PS_RNG_STREAM
-        elif rng == "philox":
-            uoff, uniforms, mode = None, None, nv.PS_RNG_PHILOX
-        else:
-            raise ValueError("rng must be 'numpy' or 'philox'")
+        uniforms, uoff, mode = _stream_plan(graph, starts, W, L, rng, uniforms, stream_nodes)
         if biased:
             woff = None
             if uoff is not None:                                 # walk w of start i: uoff[i] + w * L
@@ -346,6 +354,11 @@ def walk_sample(graph, nodes, T, W=100, L=2, rng="numpy", seed=0, call=0, unifor
                 nv.ptr(getattr(graph, "dest_info", None) if (packed and use_dest) else None),
                 nv.ptr(ids), nv.ptr(counts), nv.ptr(nvalid), nv.stream())
     return NeighborBatch(ids, counts, nvalid)
+
+
+def _range_tensor(nodes, dev):
+    """a python range of node ids as int64 on `dev` (made anew; _range_nodes caches); anything else as it is"""
+    return torch.arange(nodes.start, nodes.stop, dtype=torch.int64, device=dev) if isinstance(nodes, range) else nodes
 
 
 _range_nodes_dev = {}
@@ -377,11 +390,8 @@ def walk_sample_layers(graph, nodes, T, layers, W=100, L=2, rng="numpy", seed=0,
     if is_biased(p, q) or (rng == "numpy" and graph.has_reachable_sink):
         # a walk that reaches a sink consumes fewer uniforms: the layers are drawn one after the other, each from where the
         # previous one left the stream (what consecutive batch_sample_neighbors calls do in the reference)
-        nd = torch.arange(nodes.start, nodes.stop, dtype=torch.int64, device=dev) if isinstance(nodes, range) else nodes
-        sn = None
-        if stream_nodes is not None:
-            a0 = stream_nodes[0]
-            sn = (torch.arange(a0.start, a0.stop, dtype=torch.int64, device=dev) if isinstance(a0, range) else a0, stream_nodes[1])
+        nd = _range_tensor(nodes, dev)
+        sn = None if stream_nodes is None else (_range_tensor(stream_nodes[0], dev), stream_nodes[1])
         return [walk_sample(graph, nd, T, W, L, rng=rng, seed=seed, call=call + r, uniforms=None, stream_nodes=sn, p=p, q=q)
                 for r in range(layers)]
     as_range = nodes if isinstance(nodes, range) else None
@@ -408,12 +418,8 @@ def walk_sample_layers(graph, nodes, T, layers, W=100, L=2, rng="numpy", seed=0,
             if key is not None and key in cache:
                 uoff_all, stride = cache[key]
             else:
-                all_t = (torch.arange(src.start, src.stop, dtype=torch.int64, device=dev)
-                         if isinstance(src, range) else _nodes_tensor(src, dev, graph.V))
-                total = torch.empty(1, dtype=torch.int64, device=dev)
-                uoff_all = torch.empty(all_t.numel(), dtype=torch.int64, device=dev)
-                nv.call("ps_uniform_offsets", nv.ptr(graph.rowptr), graph.V, nv.ptr(all_t), all_t.numel(), W, L, nv.ptr(uoff_all),
-                        nv.ptr(total), nv.stream())
+                all_t = _range_tensor(src, dev) if isinstance(src, range) else _nodes_tensor(src, dev, graph.V)
+                uoff_all, total = _uniform_offsets(graph, all_t, W, L)
                 stride = int(total.item())
                 if key is not None:
                     cache[key] = (uoff_all, stride)
@@ -466,17 +472,9 @@ def walk_paths(graph, starts, L, rng="numpy", seed=0, call=0, walk_mod=0, p=1.0,
     B = int(st.numel())
     paths = torch.empty((B, L), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        if rng == "numpy" and graph.has_reachable_sink:
-            uniforms, uoff = _sink_stream(graph, st, 1, L)       # one walk per start node: W = 1
-            mode = nv.PS_RNG_STREAM
-        elif rng == "numpy":
-            uoff = torch.empty(B, dtype=torch.int64, device=dev)
-            total = torch.empty(1, dtype=torch.int64, device=dev)
-            nv.call("ps_uniform_offsets", nv.ptr(graph.rowptr), graph.V, nv.ptr(st), B, 1, L, nv.ptr(uoff), nv.ptr(total), nv.stream())
-            uniforms = draw_numpy_uniforms(int(total.item()), dev)
-            mode = nv.PS_RNG_STREAM
-        else:
-            uoff, uniforms, mode = None, None, nv.PS_RNG_PHILOX
+        uniforms, uoff, mode = _stream_plan(graph, st, 1, L, rng)
+        if mode == nv.PS_RNG_STREAM_WALKS:
+            mode = nv.PS_RNG_STREAM                              # one walk per start node: a walk's position is its node's
         if biased:
             return _biased_paths(graph, st, L, mode, uniforms, uoff, seed, call, walk_mod, p, q)
         nv.call("ps_walk_paths", nv.ptr(graph.rowptr), nv.ptr(graph.col), nv.ptr(graph.cdf), graph.V, nv.ptr(st), B, L, mode,

@@ -1,5 +1,5 @@
-"""The cases of the contract matrix (tests/helpers/abi_cases.py, tests/test_hip_abi_contract.py) for csrc/walk_biased.hip:
-ps_walk_paths_biased and ps_paths_topk.  Every output is held to tests/helpers/biased_walk_cases.py bit for bit (no eager
+"""The cases of the contract matrix (tests/helpers/abi_cases.py, tests/test_hip_abi_contract.py) for csrc/walk_biased.hip
+(ps_walk_paths_biased) and csrc/walk_topk.hip (ps_paths_topk).  Every output is held to tests/helpers/biased_walk_cases.py bit for bit (no eager
 expectation); neither entry point takes a workspace or synchronises.
 
 The builders join abi_cases' CASES table through its `case` decorator when this module is imported;

@@ -18,7 +18,7 @@ import walk_cases as wc
 V = 1 << 18
 START0, BAND = 100_000, 1024              # start node of row r: START0 + 2 r; START0 + 2 r + 1 is isolated (no edge in or out)
 RET0 = 110_000                            # RET0 + r: one edge, to the start node of row r (a walk that returns to its start)
-HASH_MULT = 2654435761                    # walk_sample.hip: h = id * 2654435761u >> (32 - hs_log2)
+HASH_MULT = 2654435761                    # walk_visits.h: h = id * 2654435761u >> (32 - hs_log2)
 MAX_P = 4096                              # walk_sample_launch: P > 4096 is unsupported
 RET = -2                                  # placeholder in a case's picks: the return node of its own row
 SLOTS = 64                                # positions per slot j: p = j * 64 + lane

@@ -1,9 +1,10 @@
-"""Node2vec-biased walks on the device (csrc/walk_biased.hip: ps_walk_paths_biased, ps_paths_topk) and the p / q of
-RandomWalkSampler, against tests/helpers/biased_walk_cases.py -- the reference's loop with the alpha multiplication, drawing from
+"""Node2vec-biased walks on the device (csrc/walk_biased.hip: ps_walk_paths_biased; csrc/walk_topk.hip: ps_paths_topk) and the
+p / q of RandomWalkSampler, against tests/helpers/biased_walk_cases.py -- the reference's loop with the alpha multiplication, drawing from
 np.random.  Every comparison is exact.
 
   1. bias {1, 1} is ps_walk_paths bit for bit (stream and Philox, walk_mod 0 and W, L 1 .. 5);
-  2. ps_paths_topk over replayed paths is ps_walk_sample's ids / counts / nvalid;
+  2. ps_paths_topk over replayed paths is ps_walk_sample's ids / counts / nvalid (both run csrc/walk_visits.h: the callers' glue),
+     and equals the restatement at every number of positions per lane and every padding edge;
   3. rng='numpy': the sampler's paths, neighbour lists, fp64 weights and np.random state equal the restatement's;
   4. planted uniforms (ties on the biased CDF, 0, 1 - 2^-53) land where np.searchsorted puts them, on a row of every degree;
   5. the surface: argument errors, graphs with sinks, from_graph, hard negatives, the sharded pipeline's refusal, the untouched
@@ -123,6 +124,37 @@ def test_paths_topk_on_hand_written_paths():
         assert np.array_equal(got.nvalid.cpu().numpy(), nvalid)
     assert ids[0, :3].tolist() == [5, 9, 2] and ids[1, :8].tolist() == [4, 3, 2, 1, 8, 7, 6, 5] and ids[2, :2].tolist() == [3, 1]
     assert nvalid.tolist() == [3, 8, 2, 0, 1]
+
+
+def _register_rows(n):
+    """five rows of n entries: many classes with ties and -1 holes; all distinct; all equal; all -1; one id at the even positions
+    among distinct ones (count ceil(n / 2) against ones)"""
+    rs = np.random.RandomState(1000 + n)
+    mixed = rs.randint(0, max(2, n // 3), size=n)
+    mixed[rs.random_sample(n) < 0.1] = -1
+    alternating = 100000 + np.arange(n)
+    alternating[::2] = 7
+    return np.stack([mixed, 10 + rs.permutation(8 * n)[:n], np.full(n, 42), np.full(n, -1), alternating]).astype(np.int32)
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 128, 129, 1023, 1024, 1025, 2049, 4095])
+def test_paths_topk_on_register_positions(n):
+    """ps_paths_topk keeps a row's positions in registers, NP = 1, 2, 4 .. 64 per lane (csrc/walk_topk.hip): n on either side of
+    every NP's last lane group and of the 33-word bitmap, n that is no multiple of 64, T below, inside and at n."""
+    from pinsage_hip import sampling
+    paths = _register_rows(n)
+    if n >= 8:                                                    # the first row has a tie between different ids
+        c = np.bincount(paths[0][paths[0] >= 0])
+        c = c[c > 0]
+        assert np.unique(c).size < c.size
+    dev = _dev(paths)
+    for T in sorted({1, 7, n}):
+        ids, counts, nvalid = bc.topk_from_paths(paths, T)
+        assert nvalid[3] == 0 and nvalid[2] == 1 and (ids[4, 0], counts[4, 0]) == (7, (n + 1) // 2)
+        got = sampling.paths_topk(dev, T)
+        assert np.array_equal(got.ids.cpu().numpy(), ids), T
+        assert np.array_equal(got.counts.cpu().numpy(), counts), T
+        assert np.array_equal(got.nvalid.cpu().numpy(), nvalid), T
 
 
 # ------------------------------------------------------------------------------------------- 3. rng='numpy' vs the restatement

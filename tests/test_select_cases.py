@@ -140,9 +140,11 @@ def test_every_slip_changes_a_named_case():
 
 
 def test_the_restated_constants_still_stand_in_the_kernel():
-    """plain text search: a change to the kernel's table arithmetic flags helpers/select_cases.py as stale"""
-    src = open(os.path.join(HERE, "..", "movie-recommendation-engine_amd", "csrc", "walk_sample.hip")).read()
-    for text in (f"* {sc.HASH_MULT}u) >> (32 - a.hs_log2)", "int hs_log2 = 6;", "(1 << hs_log2) * 4 < 5 * P", "(P >> 5) + 1",
+    """plain text search: a change to the kernel's table arithmetic flags helpers/select_cases.py as stale (the launcher and
+    its limits are in walk_sample.hip, the count / select phases and what sizes them in walk_visits.h)"""
+    csrc = os.path.join(HERE, "..", "movie-recommendation-engine_amd", "csrc")
+    src = open(os.path.join(csrc, "walk_sample.hip")).read() + open(os.path.join(csrc, "walk_visits.h")).read()
+    for text in (f"* {sc.HASH_MULT}u) >> (32 - t.hs_log2)", "int hs_log2 = 6;", "(1 << hs_log2) * 4 < 5 * P", "(P >> 5) + 1",
                  f"P > {sc.MAX_P}", "(h + 1) & (uint32_t)(HS - 1)", "const int p = j * 64 + lane;", "cr[j] >> 5], 1u << (cr[j] & 31)",
                  "while (np * 64 < P) np <<= 1;"):
         assert text in src, text
