@@ -876,6 +876,33 @@ int ps_ppr_push(const int64_t *in_rowptr, const int32_t *in_src, const double *i
 int ps_ppr_topk(const double *score, int64_t S, int64_t ld, int64_t Vp, int64_t max_target, int k, int32_t *ids, double *scores,
                 double *wts, int32_t *nvalid, ps_stream_t stream);
 
+/* ---- hard negatives by personalized-PageRank rank (PinSage paper, section 3.3: "items ranked 2000-5000"; the reference's
+ * NegativeSampler.sample_hard_negatives, data/negative_sampler.py:44-99, slices a ranking of at most 200 walked nodes, so its
+ * window is always empty), csrc/rank_window.hip.
+ * ps_rank_window: score double[S, ld] (ld >= Vp): source-major rows as ps_ppr_topk reads them.  limit = max_target if
+ *   0 <= max_target < Vp, else Vp (ps_ppr_topk's rule).  The ranking population of row s is the ids t < limit with
+ *   score[s,t] > 0 and t != skip[s] (skip int64[S]; NULL, or an entry outside [0, limit), skips nothing).  NaN, zeros of either
+ *   sign and negative scores never compete; +inf does.  Columns in [limit, ld) are never candidates, columns in [Vp, ld) are
+ *   never read.  Order: ps_ppr_topk's -- score descending, ties to the smaller id; ranks count from 0.
+ *   window int32[S, hi - lo]: the ids whose rank r satisfies lo <= r < hi, in ASCENDING ID order (the consumer samples a set;
+ *   no sort is needed), then -1 pads: the row is fully written.  nwin int32[S] = their number.  limit == 0 or a row without
+ *   candidates: nwin = 0, all pads.
+ *   Picks (n > 0; u double[S, n], picks int32[S, n]): Floyd's subset sampling over the window's positions.  With m = nwin[s],
+ *   c = min(n, m), for i = 0 .. c-1:  j = m - c + i;  t = min((int64)floor(u[s,i] * (j + 1)), j), one fp64 product, t = 0 for a
+ *   negative or NaN u;  p_i = j if t is among p_0 .. p_{i-1}, else t;  picks[s,i] = window[s, p_i].  Slots i >= c get -1.  Every
+ *   c-subset of the window has the same probability under independent uniform u.  (For u < 1 the rounded product stays below
+ *   j + 1, so the floor alone gives t <= j; the clamp answers a u at or above 1, infinity included.)  With n == 0,
+ *   u and picks may be NULL and are not touched.
+ *   One launch, one workgroup per row, no workspace: an MSB-first radix select over the 64-bit patterns of the positive scores
+ *   (eight sweeps of the row, both boundaries at once), one more sweep that emits the members.  No float arithmetic decides
+ *   anything but the one product above; integer LDS atomics only: the same inputs give the same bytes on every run.
+ *   PS_EINVAL: negative S, Vp or n; ld < Vp; lo < 0; hi <= lo; S, Vp or hi at or above 2^31.  Then PS_OK for S == 0, nothing
+ *   touched.  Then PS_EINVAL for a NULL score (with Vp > 0), window or nwin, or n > 0 with a NULL u or picks.  Then
+ *   PS_EUNSUPPORTED for hi - lo > ps_rank_window_max() (65 536) or n > 64.  All checked before anything is enqueued. */
+int ps_rank_window_max(void);
+int ps_rank_window(const double *score, int64_t S, int64_t ld, int64_t Vp, int64_t max_target, const int64_t *skip, int64_t lo,
+                   int64_t hi, const double *u, int n, int32_t *window, int32_t *nwin, int32_t *picks, ps_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,8 @@ PROTOTYPES = {
     "ps_ppr_push_workspace_bytes": "z qq",
     "ps_ppr_push": "i pppqqppipqQiippzp",
     "ps_ppr_topk": "i pqqqqippppp",
+    "ps_rank_window_max": "i",
+    "ps_rank_window": "i pqqqqpqqpipppp",
 }
 SYMBOLS = list(PROTOTYPES)
 

@@ -93,7 +93,7 @@ def _chunk(S, Vp, device, source_chunk):
 
 
 def _push_chunks(graph, sources, alpha, sweeps, source_chunk, skip_rows):
-    """yields (lo, n, score_t fp64[n, Vp] source-major) per chunk of source columns"""
+    """yields (lo, n, score_t fp64[n, Vp] source-major, the chunk's sources int64[n] on the device) per chunk of source columns"""
     _check(alpha, sweeps)
     pg = ppr_graph(graph)
     dev = pg.device
@@ -113,14 +113,14 @@ def _push_chunks(graph, sources, alpha, sweeps, source_chunk, skip_rows):
                     pg.level_ptr.ctypes.data, pg.n_levels, nv.ptr(src[lo:lo + n]), n, alpha_bits, int(sweeps), flags,
                     nv.ptr(score), nv.ptr(ws), ws_bytes, nv.stream())
             del ws
-            yield lo, n, score[:, :n].t().contiguous()
+            yield lo, n, score[:, :n].t().contiguous(), src[lo:lo + n]
 
 
 def ppr_scores(graph, sources, alpha=0.15, sweeps=10, source_chunk=None, skip_rows=True):
     """fp64[S, V'] on the device: row i = the reference's `ppr` vector of sources[i] after `sweeps` push sweeps
     (utils/random_walk.py:163-188), V' = max(V, max(sources) + 1); a source >= V is a node without edges.  Sources run in
     chunks of columns sized from free memory (multiples of 64); `source_chunk` sets the chunk size."""
-    rows = [t for _, _, t in _push_chunks(graph, sources, alpha, sweeps, source_chunk, skip_rows)]
+    rows = [t for _, _, t, _ in _push_chunks(graph, sources, alpha, sweeps, source_chunk, skip_rows)]
     if not rows:
         return torch.zeros((0, graph.V), dtype=torch.float64, device=graph.device)
     return rows[0] if len(rows) == 1 else torch.cat(rows, 0)
@@ -142,7 +142,7 @@ def ppr_topk(graph, sources, k=10, alpha=0.15, sweeps=10, max_target=None, sourc
     mt = -1 if max_target is None else int(max_target)
     if max_target is not None and mt < 0:
         raise ValueError("max_target must not be negative")
-    for lo, n, rows in _push_chunks(graph, sources, alpha, sweeps, source_chunk, skip_rows):
+    for lo, n, rows, _ in _push_chunks(graph, sources, alpha, sweeps, source_chunk, skip_rows):
         Vp = int(rows.size(1))
         with torch.cuda.device(dev):
             nv.call("ps_ppr_topk", nv.ptr(rows), n, Vp, Vp, mt, k, nv.ptr(ids[lo:lo + n]), nv.ptr(scores[lo:lo + n]),
@@ -150,3 +150,39 @@ def ppr_topk(graph, sources, k=10, alpha=0.15, sweeps=10, max_target=None, sourc
     batch = WeightedBatch(ids, wts, nvalid)
     batch.scores = scores
     return batch
+
+
+def ppr_rank_window(graph, sources, lo, hi, *, n=0, uniforms=None, alpha=0.15, sweeps=10, max_target=None, skip_self=True,
+                    source_chunk=None, skip_rows=True):
+    """-> (window int32[S, hi - lo], nwin int32[S], picks int32[S, n] or None) on the device: per source the targets whose rank
+    in ppr_topk's order (score descending, ties to the smaller id, 0-based) lies in [lo, hi), in ascending id order with -1
+    pads, and with n > 0 a Floyd subset of them drawn from `uniforms` fp64[S, n] (ps_rank_window, include/pinsage_hip.h).  Only
+    targets below `max_target` compete when it is given; skip_self leaves the source itself out of its own ranking."""
+    lo, hi, n = int(lo), int(hi), int(n)
+    if lo < 0 or hi <= lo:
+        raise ValueError("the rank window needs 0 <= lo < hi")
+    if hi - lo > nv.lib().ps_rank_window_max():
+        raise ValueError(f"the rank window holds at most {nv.lib().ps_rank_window_max()} ranks")
+    if n < 0:
+        raise ValueError("n must not be negative")
+    dev = graph.device
+    S = int(len(sources)) if not isinstance(sources, torch.Tensor) else int(sources.numel())
+    u = None
+    if n > 0:
+        if uniforms is None or tuple(np.shape(uniforms)) != (S, n):
+            raise ValueError(f"n = {n} picks need uniforms of shape [{S}, {n}]")
+        u = uniforms if isinstance(uniforms, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(uniforms, dtype=np.float64))
+        u = u.to(device=dev, dtype=torch.float64).contiguous()
+    mt = -1 if max_target is None else int(max_target)
+    if max_target is not None and mt < 0:
+        raise ValueError("max_target must not be negative")
+    window = torch.empty((S, hi - lo), dtype=torch.int32, device=dev)
+    nwin = torch.empty(S, dtype=torch.int32, device=dev)
+    picks = torch.empty((S, n), dtype=torch.int32, device=dev) if n > 0 else None
+    for c0, c, rows, src in _push_chunks(graph, sources, alpha, sweeps, source_chunk, skip_rows):
+        Vp = int(rows.size(1))
+        with torch.cuda.device(dev):
+            nv.call("ps_rank_window", nv.ptr(rows), c, Vp, Vp, mt, nv.ptr(src if skip_self else None), lo, hi,
+                    nv.ptr(u[c0:c0 + c] if n > 0 else None), n, nv.ptr(window[c0:c0 + c]), nv.ptr(nwin[c0:c0 + c]),
+                    nv.ptr(picks[c0:c0 + c] if n > 0 else None), nv.stream())
+    return window, nwin, picks

@@ -167,6 +167,13 @@ class RandomWalkSampler:
         nodes = nodes.tolist() if isinstance(nodes, torch.Tensor) else list(nodes)
         return ppr.ppr_topk(self.graph, nodes, int(num_neighbors), alpha, num_iterations, max_target=max_target)
 
+    def ppr_rank_window(self, nodes, min_rank, max_rank, **kw):
+        """-> (window int32[B, max_rank - min_rank], nwin int32[B], picks or None) on the device: per node the targets ranked
+        [min_rank, max_rank) by PPR, ascending id, -1 pads (pinsage_hip.ppr.ppr_rank_window takes the keywords)."""
+        from pinsage_hip import ppr
+        nodes = nodes.tolist() if isinstance(nodes, torch.Tensor) else list(nodes)
+        return ppr.ppr_rank_window(self.graph, nodes, min_rank, max_rank, **kw)
+
     def _ppr_on_device(self):
         if self.ppr_method not in ("device", "host"):
             raise ValueError(f"ppr_method must be 'device' or 'host', not {self.ppr_method!r}")
